@@ -13,7 +13,16 @@ strong scaling. `--config 2` (100 spp, brute force) and `--config 5` (3840x2160,
 Random stream (`--rng`): "hash" (default; RT_RNG_SAMPLE_HASH, the north star's counter-based RNG:
 per-sample LCG starts, fixed-point sums, samples of a pixel split into chunks over the lanes) or
 "stream" (the reference's per-pixel LCG stream). Both are bit-exact against the CPU oracle; the
-N = 1 line also times the other stream on the same frame (`reference_stream`).
+`--full` N = 1 line also times the other stream on the same frame (`reference_stream`).
+
+A plain run does only what the headline needs: set-up, the warm-up frames, the `--steps` timed
+frames, and one JSON line with the headline fields (`metric`, `value`, `unit`, `ms_per_step`, ...,
+`config`, `build`). `--full` adds everything else, each in runs of its own after the timed region:
+the rebuild check of the library, the instrumented launch and its `roofline`, `scene_call_ms`, the
+side lines (other stream, LBVH walk, brute force, config 5, animated loop, cold `ray_trace` call),
+`cpu_baseline` with its parity checks, and `n1_check` at N > 1. `--dump-outputs DIR` writes the
+last timed frame as the caller receives it (`DIR/accum.npy`, `DIR/rgba8.npy`, float32); the scene,
+the camera and the seeds are fixed, so two builds can be compared output for output.
 
 Launch modes (the line's config.path names the one that ran):
   python bench.py [--gpus 1 --steps 3 --warmup 1]         single: one Renderer on one GPU
@@ -458,6 +467,28 @@ def cold_call_line(W: int, H: int, spp: int, timeout_s: int = 300) -> dict:
                     "frame without LPT history (frame_ms), teardown"}
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # all files of one --dump-outputs directory together
+
+
+def dump_outputs(path, accum, rgba8) -> dict:
+    """Writes the frame the timed path returned (numpy [H, W, 4]: float32 accumulator, uint8 rgba8)
+    as path/accum.npy and path/rgba8.npy, both float32. A frame above the byte budget is reduced to
+    a fixed sample of its pixels, the same for both arrays and for every run of one frame size
+    (seed 0, sorted pixel indices, shape [n, 4]); BASELINE config 3's frame keeps 93 % of them."""
+    import numpy as np
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    h, w = accum.shape[:2]
+    n = min(h * w, DUMP_BUDGET_BYTES // (2 * 4 * 4))
+    arrays = {"accum": accum, "rgba8": rgba8}
+    if n < h * w:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+        arrays = {k: v.reshape(h * w, 4)[idx] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(path / f"{k}.npy", np.ascontiguousarray(v, dtype=np.float32))
+    return {"dir": str(path), "files": [f"{k}.npy" for k in arrays], "pixels": int(n), "of": int(h * w)}
+
+
 def env_knobs() -> dict:
     """RT_* variables of this process. The library reads only RT_RNG (ray_trace(), not this bench's
     path) and RT_BVH_BUILD; rtvk reads RT_LIB (another library); bench.py reads RT_BENCH_BACKEND
@@ -487,6 +518,14 @@ def main() -> int:
     ap.add_argument("--count-spp", type=int, default=100,
                     help="spp of the instrumented (test-counting) launch; its counts are scaled to the frame's "
                          "spp (per-sample statistics are stationary: same scene, same streams)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run everything beyond the headline: the rebuild check, the "
+                         "instrumented launch and roofline, scene_call_ms, the side lines, cpu_baseline with its "
+                         "parity checks, n1_check at N > 1 (the --no-* options below take legs out of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (accumulator and rgba8, as the caller receives them) to "
+                         "DIR/accum.npy and DIR/rgba8.npy in float32; a frame above 60 MB in all is reduced to a "
+                         "fixed seeded sample of its pixels")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side-lines", action="store_true",
                     help="skip the other-stream, LBVH-walk and brute-force lines")
@@ -501,6 +540,8 @@ def main() -> int:
                     help="frames in flight (single path): contexts + streams used round robin. Default 1: with "
                          "sample chunks the tail is short and a second frame only interferes (DESIGN.md §6)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     W0, H0, spp0, grid0, accel0 = CONFIGS[args.config]
     W, H = args.width or W0, args.height or H0
     spp = args.spp if args.spp is not None else spp0
@@ -545,7 +586,7 @@ def main() -> int:
         print("error: --path single renders on one GPU; use --gpus 1", file=sys.stderr)
         return 2
     rebuild = None
-    if not args.no_rebuild_check and not args.profile and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and not args.no_rebuild_check and not args.profile and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # Build provenance: compile the library from this tree's sources on this machine and compare
         # it with the shipped binary; when they differ, the fresh binary replaces it before it loads.
         import shutil
@@ -685,7 +726,7 @@ def main() -> int:
         kernel_ms = sum(ks) / max(1, len(ks))
         k_basis = (f"mean trace-kernel duration of the {len(ks)} launches of the timed region (HIP events "
                    f"recorded by the library around the kernel on its launch stream)")
-        if len(slots) > 1:
+        if len(slots) > 1 and args.full:
             # with frames in flight a launch's events also span the wait for CUs the other slot's
             # frame holds: time 3 frames alone (one at a time) for the kernel's own duration
             for _ in range(3):
@@ -710,16 +751,18 @@ def main() -> int:
     step_ms = elapsed / args.steps * 1e3
 
     # Algorithmic work of one frame, counted by the instrumented build of the same kernel
-    # (identical image, same traversal; outside the timed region).
+    # (identical image, same traversal; outside the timed region; --full only).
+    cs = rtvk.Stats()
     if mode == "multi":
         st = mr.stats()
         info = None
-        ca = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
-        co = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda:0")
-        mr.render(cnt_rci, ca, co, options=cnt_opts)
-        sync_all()
-        cs = mr.stats()
-        del ca, co
+        if args.full:
+            ca = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda:0")
+            co = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda:0")
+            mr.render(cnt_rci, ca, co, options=cnt_opts)
+            sync_all()
+            cs = mr.stats()
+            del ca, co
         multi_info = mr.info()
         # the walk form of device 0's context (every device renders the same scene the same way)
         probe = rtvk.Renderer(0)
@@ -735,15 +778,13 @@ def main() -> int:
         st = renderer.stats()   # this rank's last band
         info = renderer.launch_info()
         device_built = renderer.scene_array(8)["device_built"]
-        if dr.n:
+        if dr.n and args.full:
             acc = torch.zeros((dr.n, W, 4), dtype=torch.float32, device=dev)
             out = torch.zeros((dr.n, W, 4), dtype=torch.uint8, device=dev)
             renderer.render_device(cnt_rci, acc, out, rows=dr.rows, options=cnt_opts)
             sync_all()
             cs = renderer.stats()
             del acc, out
-        else:
-            cs = rtvk.Stats()
         if mode == "per-process":   # whole-frame counts: sum over the ranks
             t = torch.tensor([cs.box_tests, cs.sphere_tests, st.segments, st.samples], dtype=torch.float64,
                              device=dev)
@@ -754,15 +795,17 @@ def main() -> int:
     # host cost of one per-frame scene call with the GPU idle (host build + upload issue for host
     # scenes; for device builds it includes the build, which in the timed loop overlaps the
     # previous frame): the per-frame setup a rank pays outside the kernel
-    sync_all()
-    t_sc = time.perf_counter()
-    for _ in range(5):
-        if mode == "multi":
-            mr.set_scene(scene)
-        else:
-            renderer.set_scene(scene)
-    scene_call_ms = (time.perf_counter() - t_sc) / 5 * 1e3
-    sync_all()
+    scene_call_ms = None
+    if args.full:
+        sync_all()
+        t_sc = time.perf_counter()
+        for _ in range(5):
+            if mode == "multi":
+                mr.set_scene(scene)
+            else:
+                renderer.set_scene(scene)
+        scene_call_ms = (time.perf_counter() - t_sc) / 5 * 1e3
+        sync_all()
 
     samples_per_step = W * H * spp
     value = samples_per_step * args.steps / elapsed / 1e6
@@ -771,8 +814,10 @@ def main() -> int:
     if rank == 0:
         sha = lib_sha256()
         key = f"{accel_name}-{args.rng}-{W}x{H}-{spp}spp-grid{grid}-n{n_gpus}"
-        pmc = pmc_record(key, sha)
-        if accel == abi.RT_ACCEL_BRUTE:
+        pmc = pmc_record(key, sha) if args.full else {}
+        if not args.full:
+            roof = None
+        elif accel == abi.RT_ACCEL_BRUTE:
             flops = st.segments * len(scene) * FLOP_PER_SPHERE_TEST
             peak = VALU_FP32_PEAK_TFLOPS * n_gpus
             ach = flops / (kernel_ms * 1e-3) / 1e12 if kernel_ms > 0 else 0.0
@@ -826,9 +871,9 @@ def main() -> int:
                        "frames_in_flight": 1 if mode == "multi" else len(slots)},
             "segments_per_sample": round(st.segments / max(1, st.samples), 4),
             "scene_setup_ms": round(t_scene * 1e3, 2),
-            "scene_call_ms": round(scene_call_ms, 3),
             "msegments_per_s": round(st.segments / max(1, st.samples) * value, 2),
-            "roofline": roof,
+            **({"scene_call_ms": round(scene_call_ms, 3), "roofline": roof} if args.full else {}),
+            "full": bool(args.full),
             "build": {**abi.build_info(), "env": knobs,
                       "rebuild": rebuild if rebuild is not None else "skipped"},
             **({"rehearsal": f"{backend} backend, {world} ranks sharing {n_vis} GPU(s): "
@@ -838,20 +883,21 @@ def main() -> int:
         }
         fa, fo = last
         if n_gpus > 1:
-            # N > 1 verifies itself: the gathered frame against this frame rendered on ONE GPU
-            r1 = rtvk.Renderer(local)
-            r1.set_scene(scene)
-            a1 = torch.zeros((H, W, 4), dtype=torch.float32, device=dev)
-            o1 = torch.zeros((H, W, 4), dtype=torch.uint8, device=dev)
-            r1.render_device(rci, a1, o1, options=opts)
-            torch.cuda.synchronize(dev)
-            fa_d, fo_d = fa.to(dev), fo.to(dev)
-            result["n1_check"] = {
-                "pixels": W * H, "accum_bit_equal": bool(torch.equal(fa_d, a1)),
-                "rgba8_equal": bool(torch.equal(fo_d, o1)),
-                "what": "gathered N-GPU frame vs the same frame rendered by one GPU (same seeds, same stream)"}
+            if args.full:
+                # N > 1 verifies itself: the gathered frame against this frame rendered on ONE GPU
+                r1 = rtvk.Renderer(local)
+                r1.set_scene(scene)
+                a1 = torch.zeros((H, W, 4), dtype=torch.float32, device=dev)
+                o1 = torch.zeros((H, W, 4), dtype=torch.uint8, device=dev)
+                r1.render_device(rci, a1, o1, options=opts)
+                torch.cuda.synchronize(dev)
+                fa_d, fo_d = fa.to(dev), fo.to(dev)
+                result["n1_check"] = {
+                    "pixels": W * H, "accum_bit_equal": bool(torch.equal(fa_d, a1)),
+                    "rgba8_equal": bool(torch.equal(fo_d, o1)),
+                    "what": "gathered N-GPU frame vs the same frame rendered by one GPU (same seeds, same stream)"}
+                r1.close()
             result["rccl_ranks"] = multi_info["rccl_ranks"] if mode == "multi" else world
-            r1.close()
             if per_device_ms:
                 mean = sum(per_device_ms) / len(per_device_ms)
                 result["per_device_kernel_ms"] = [round(v, 3) for v in per_device_ms]
@@ -867,12 +913,14 @@ def main() -> int:
                                              "the timed frames (HIP events on its launch stream); rows_per_device: "
                                              "the balancer's partition after the timed frames (row-exact strips "
                                              "re-dealt from the kernel times of the frame two before)")
-        if n_gpus == 1:
+        if n_gpus == 1 or args.dump_outputs:
             frame_np = (fa.cpu().numpy(), fo.cpu().numpy())
+        if args.dump_outputs:
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, *frame_np)
     # Side lines (single GPU): the same frame with the other random stream and with the LBVH walk
     # (BASELINE config 3 names LBVH traversal), and BASELINE configs 2 and 5 as specified.
     other_frame = None
-    if mode == "single" and not args.no_side_lines and not args.profile:
+    if mode == "single" and args.full and not args.no_side_lines and not args.profile:
         def time_frames(o, w, h, s, n):
             a = torch.zeros((h, w, 4), dtype=torch.float32, device=dev)
             b = torch.zeros((h, w, 4), dtype=torch.uint8, device=dev)
@@ -942,7 +990,7 @@ def main() -> int:
                 cold["vs_headline"] = round(cold["value"] / result["value"], 4)
             result["ray_trace_call"] = cold
             result["ray_trace_call_s"] = cold.get("call_s")
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.profile:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline and not args.profile:
         result["cpu_baseline"] = cpu_baseline(W, H, spp, grid, rng_mode, frame_np[0], frame_np[1], other=other_frame)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line with the driver's fields, roofline and cpu_baseline),
-on a tiny workload through the real library."""
+"""bench.py's output contract (one JSON line with the driver's fields; with --full the roofline,
+side lines and cpu_baseline too; --dump-outputs), on a tiny workload through the real library."""
 import json
 import subprocess
 import sys
@@ -13,7 +13,7 @@ ROOT = Path(__file__).resolve().parent.parent
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--width", "96", "--height", "64", "--spp", "2",
-                        "--steps", "3", "--warmup", "1", "--no-rebuild-check"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-rebuild-check"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -53,12 +53,71 @@ def test_bench_json_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_frame(tmp_path, oracle):
+    """Without --full the line carries the headline and its labels only (no roofline, CPU baseline,
+    side lines or rebuild check), and --dump-outputs writes the last timed frame: float32, equal to
+    the oracle's frame of the same scene, camera and seeds bit for bit."""
+    import numpy as np
+    W, H, spp = 72, 40, 3
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--width", str(W), "--height", str(H),
+                        "--spp", str(spp), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config", "build"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "Msamples/s"
+    assert d["value"] == pytest.approx(W * H * spp / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-2)
+    assert d["full"] is False and d["build"]["rebuild"] == "skipped"
+    for k in ("roofline", "cpu_baseline", "scene_call_ms", "reference_stream", "lbvh_walk", "brute_force", "config5",
+              "animated", "ray_trace_call"):
+        assert k not in d, k
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["accum.npy", "rgba8.npy"]
+    acc, px = np.load(tmp_path / "out" / "accum.npy"), np.load(tmp_path / "out" / "rgba8.npy")
+    assert acc.dtype == np.float32 and px.dtype == np.float32 and acc.shape == px.shape == (H, W, 4)
+    ref_acc, ref_px, _ = oracle.render(oracle.generate_scene(0.0), oracle.render_call_info(spp, W, H), W, H,
+                                       opts=oracle.options(rng_mode=2))
+    np.testing.assert_array_equal(acc, ref_acc)
+    np.testing.assert_array_equal(px, ref_px.astype(np.float32))
+
+
+def test_dump_outputs_samples_a_large_frame(tmp_path, monkeypatch):
+    """A frame above the byte budget is written as one fixed sample of its pixels: the same pixels
+    in both arrays and in every run, within the budget."""
+    import numpy as np
+    import bench
+    H, W = 37, 53
+    rng = np.random.default_rng(5)
+    acc = rng.random((H, W, 4), dtype=np.float32)
+    px = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+    whole = bench.dump_outputs(tmp_path / "whole", acc, px)
+    assert whole["pixels"] == H * W
+    np.testing.assert_array_equal(np.load(tmp_path / "whole" / "accum.npy"), acc)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1000 * 32)
+    a = bench.dump_outputs(tmp_path / "a", acc, px)
+    b = bench.dump_outputs(tmp_path / "b", acc, px)
+    assert a["pixels"] == b["pixels"] == 1000 and a["of"] == H * W
+    sa, sp = np.load(tmp_path / "a" / "accum.npy"), np.load(tmp_path / "a" / "rgba8.npy")
+    assert sa.dtype == sp.dtype == np.float32 and sa.shape == sp.shape == (1000, 4)
+    assert sa.nbytes + sp.nbytes <= 1000 * 32
+    np.testing.assert_array_equal(sa, np.load(tmp_path / "b" / "accum.npy"))
+    # the sampled pixels are distinct pixels of the frame, the same ones in both arrays
+    flat = {tuple(v): i for i, v in enumerate(acc.reshape(-1, 4))}
+    idx = [flat[tuple(v)] for v in sa]
+    assert len(set(idx)) == 1000 and idx == sorted(idx)
+    np.testing.assert_array_equal(sp, px.reshape(-1, 4)[idx].astype(np.float32))
+
+
+@pytest.mark.gpu
 def test_bench_multi_path_one_gpu():
     """--path multi: the C-ABI rt_multi path (one process; strips + RCCL gather at N > 1) on the
     box's one GPU; labelled as such: one device renders straight into the caller's buffers and
     holds no communicator."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--width", "96", "--height", "64", "--spp", "2",
-                        "--steps", "2", "--warmup", "1", "--path", "multi", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--path", "multi", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
