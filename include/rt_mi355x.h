@@ -182,6 +182,53 @@ int rt_refit_scene_device(rt_context* ctx, const Sphere* d_spheres, uint32_t cou
 int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
                      uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
                      uint8_t* out_rgba8, const rt_options* opt, void* stream);
+/*
+ * Adaptive frame of the counter-based stream: "render to this noise level, at
+ * most rci->samplesPerRenderCall (max_spp) samples per pixel". Pass 0 renders samples
+ * [0, min_spp) on every 8x8 tile of the band; every later pass renders the next
+ * min(step_spp, max_spp - done) samples on the tiles that have not converged. Each pass is two
+ * trace launches, the first half of its samples into fixed-point half-buffer A and the second into
+ * B; a tile converges when the difference of the two halves, summed over its in-band pixels and
+ * channels, is small against their sum:
+ *     E = sum |A - B|,  S = sum (A + B),  S' = S + n * 3 * m * 2^16   (n samples, m pixels)
+ *     converged  iff  2^17 * E < thr_q16 * S',   thr_q16 = floor(threshold * 65536 + 0.5)
+ * in exact integer arithmetic (rt_adaptive_tile_converged is the same function on the host).
+ * Threshold 0 never converges (every tile reaches max_spp), threshold 16 always does after pass 0.
+ * A pixel of a tile that stopped at n samples holds, bit for bit, what rt_render_device gives at
+ * samplesPerRenderCall = n with the same options: accum = the sum, rgba8 = unorm8(sqrt(sum / n)).
+ *   sample_count   optional DEVICE array of band_width * band_height uint32: n per texel.
+ *   opt            rng_mode must be RT_RNG_SAMPLE_HASH and accumulate 0; sample_base + max_spp must
+ *                  fit 32 bits; max_spp, min_spp and step_spp are even, min_spp <= max_spp <= 2^19.
+ *   info           optional, filled on return.
+ * Synchronisation: the call's device work is ordered on `stream` like rt_render_device's, but the
+ * call is synchronous per pass: it blocks the host once per pass on a small readback of the next
+ * pass's tile count (pinned memory, an event on `stream`, no device-wide synchronisation) and
+ * returns once the final resolve is queued; the outputs are valid after `stream` completes.
+ * rt_get_stats reports the last trace launch (the last half-pass) only, totals come back in
+ * `info`; each half-pass counts as one launch for rt_launch_ms. Adaptive calls neither read nor
+ * update the tile order of later rt_render_device launches and record no row weights.
+ */
+typedef struct rt_adaptive {
+    uint32_t min_spp;    /* even, >= 2; samples every pixel gets                      */
+    uint32_t step_spp;   /* even, >= 2; samples added per later pass                  */
+    float    threshold;  /* finite, 0 <= threshold <= 16; see criterion               */
+    uint32_t reserved;   /* 0 */
+} rt_adaptive;
+typedef struct rt_adaptive_info {
+    uint32_t passes;          /* passes run (1 .. 1 + ceil((max-min)/step))          */
+    uint32_t tiles;           /* 8x8 tiles of the band                               */
+    uint32_t tiles_capped;    /* tiles that reached max_spp unconverged              */
+    uint32_t reserved;
+    uint64_t samples;         /* camera samples rendered (sum of in-band n)          */
+} rt_adaptive_info;
+int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                              uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
+                              uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
+                              const rt_adaptive* ad, rt_adaptive_info* info, void* stream);
+/* The stop criterion above for one tile (host only, no device needed): *converged = 1 or 0.
+ * E, S < 2^56, n <= 2^19, 1 <= m <= 64 (RT_ERR_INVALID_ARGUMENT otherwise). */
+int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16,
+                               int* converged);
 /* Statistics of the last completed rt_render_device (synchronises ctx's last stream). */
 int rt_get_stats(rt_context* ctx, rt_stats* out);
 /* Trace-kernel duration (ms, HIP events on the launch stream) of ctx's launch `back` launches

@@ -21,6 +21,7 @@
 #include "../../include/rt_abi.h"
 #include "../../include/rt_mi355x.h"
 #include "../../include/rt_mi355x_debug.h"
+#include "rt_adaptive.h"
 #include "rt_build.h"
 #include "rt_bvh.h"
 #include "rt_grid.h"
@@ -44,6 +45,12 @@ hipError_t launch_gather_rows(const float* src_acc, const uint32_t* rows, uint32
                               uint32_t src_rows, float* dst_acc, hipStream_t st);
 hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st);
 hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st);
+// rt_adaptive.hip
+hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st);
+hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);
+hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
+                                   uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
+                                   uint32_t* sample_count, hipStream_t st);
 }  // namespace rt
 
 // Launch-plan parameters that tests and A/B scripts vary through rt_debug_tune() (per context; the
@@ -179,6 +186,18 @@ struct rt_context {
     CostSnap snap[kSnaps];
     bool keep_snaps = false;   // set by the first rt_launch_row_weights (or rt_multi at N > 1):
                                // a one-device frame loop pays no copies it never reads
+    // Adaptive frames (rt_render_adaptive_device) keep their own buffers, so they
+    // leave `fixed` and `sched` alone.
+    struct Adaptive {
+        unsigned long long* planes = nullptr;   // half-buffers A then B, 3 planes of the band's texels
+                                                // each; zero between calls (the resolve clears them)
+        uint64_t cap = 0;                       // texels the allocation holds (x 6 planes)
+        uint32_t* tiles = nullptr;              // per tile: sample count, the two tile lists and the
+        uint64_t cap_tiles = 0;                 // walk kernels' cost scratch: 4 x cap_tiles words
+        rt::AdaptiveState* state = nullptr;     // device
+        rt::AdaptiveState* host = nullptr;      // pinned copy, read after `ev` once per pass
+        hipEvent_t ev = nullptr;
+    } adaptive;
 };
 
 namespace {
@@ -566,6 +585,11 @@ int rt_context_destroy(rt_context* ctx) {
     }
     if (ctx->d_spheres) (void)hipFree(ctx->d_spheres);
     if (ctx->fixed) (void)hipFree(ctx->fixed);
+    if (ctx->adaptive.planes) (void)hipFree(ctx->adaptive.planes);
+    if (ctx->adaptive.tiles) (void)hipFree(ctx->adaptive.tiles);
+    if (ctx->adaptive.state) (void)hipFree(ctx->adaptive.state);
+    if (ctx->adaptive.host) (void)hipHostFree(ctx->adaptive.host);
+    if (ctx->adaptive.ev) (void)hipEventDestroy(ctx->adaptive.ev);
     if (ctx->counters) (void)hipFree(ctx->counters);
     delete ctx;
     return RT_OK;
@@ -1019,41 +1043,38 @@ uint32_t choose_accel(const rt_context* ctx, bool brute, uint32_t form, float ca
     return accel;
 }
 
-}  // namespace
+// The launch parameters rt_render_device and rt_render_adaptive_device share: everything that
+// does not depend on how the band's samples are split into units.
+struct TraceSetup {
+    rt::TraceParams P;
+    uint32_t accel = 0;          // kernel form (rt::ACCEL_*)
+    bool count = false;          // instrumented build (options.reserved[0] bit 0)
+    bool flat = false;           // one-layer grid walk
+    int mode = 0, ci = 0;        // rt::MODE_*, index of the occupancy cache
+    size_t lds = 0;              // dynamic LDS bytes
+    uint64_t blk = 0, lanes = 0; // block size, lanes of a full grid
+    uint64_t tiles_x = 0, n_tiles = 0;
+};
 
-extern "C" {
-
-int rt_set_scene(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream) {
-    return scene_call(ctx, spheres, count, false, stream, false);
-}
-
-int rt_set_scene_device(rt_context* ctx, const Sphere* d_spheres, uint32_t count, void* stream) {
-    return scene_call(ctx, d_spheres, count, true, stream, false);
-}
-
-int rt_refit_scene(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream) {
-    // without a device-built tree of this count there is no topology to reuse: a full build
-    return scene_call(ctx, spheres, count, false, stream, true);
-}
-
-int rt_refit_scene_device(rt_context* ctx, const Sphere* d_spheres, uint32_t count, void* stream) {
-    return scene_call(ctx, d_spheres, count, true, stream, true);
-}
-
-int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
-                     uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
-                     const rt_options* opt, void* stream) {
+// Argument checks of a render call `who`, before any device work; o = *opt or zeros. *empty: a
+// band without texels, nothing to render.
+int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t band_width, uint32_t band_height,
+                      const float* accum, const uint8_t* out, const rt_options* opt, const char* who, rt_options& o,
+                      bool* empty) {
+    *empty = false;
     if (!ctx || !rci) return fail(RT_ERR_INVALID_ARGUMENT, "ctx or rci is NULL");
-    if (ctx->pending) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_device between the halves of a scene build");
-    if (!ctx->scene_set) return fail(RT_ERR_NO_SCENE, "rt_render_device before rt_set_scene");
-    if (band_width == 0 || band_height == 0) return RT_OK;
+    if (ctx->pending) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " between the halves of a scene build");
+    if (!ctx->scene_set) return fail(RT_ERR_NO_SCENE, std::string(who) + " before rt_set_scene");
+    if (band_width == 0 || band_height == 0) {
+        *empty = true;
+        return RT_OK;
+    }
     if (!accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "accum or out is NULL");
     if (rci->image_size.x == 0 || rci->image_size.y == 0)
         return fail(RT_ERR_INVALID_ARGUMENT, "image_size is zero");
     // the kernel keeps a pixel's band coordinates as 16-bit halves of one word (Path::px)
     if (band_width > 65535u || band_height > 65535u)
         return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be below 65536");
-    rt_options o;
     std::memset(&o, 0, sizeof(o));
     if (opt) o = *opt;
     if (o.accel > RT_ACCEL_LBVH) return fail(RT_ERR_INVALID_ARGUMENT, "unknown accel");
@@ -1070,6 +1091,16 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         return fail(RT_ERR_INVALID_ARGUMENT,
                     "RT_RNG_SAMPLE_HASH needs every sphere colour channel in [0, 1] (colors[0], and colors[1] of "
                     "checkered spheres); this scene has one outside: render it with RT_RNG_PIXEL_STREAM");
+    (void)mode;
+    return RT_OK;
+}
+
+// Scene pointers, camera, cull slack, re-pad of a far camera, the row map's place and the
+// occupancy of the kernel form, on the caller's device and stream (after order_on).
+int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+               uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, TraceSetup& S) {
+    const int mode = o.rng_mode == RT_RNG_SAMPLE_HASH ? rt::MODE_HASH : rt::MODE_STREAM;
+    const uint32_t spp = rci->samplesPerRenderCall;
     const uint64_t tiles_x = (band_width + 7u) / 8u, tiles_y = (band_height + 7u) / 8u;
     const uint64_t n_tiles = tiles_x * tiles_y;
     // reserved[1] (internal, A/B only): walk form, 0 = automatic (choose_accel)
@@ -1079,10 +1110,6 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
     size_t lds = 0;
     const uint32_t accel = choose_accel(ctx, o.accel == RT_ACCEL_BRUTE, o.reserved[1], cam_r, &lds);
     const bool count = (o.reserved[0] & 1u) != 0;  // internal: count box / sphere tests
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;
-
     rt::TraceParams P;
     std::memset(&P, 0, sizeof(P));
     fill_camera(*rci, P);
@@ -1203,17 +1230,39 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
     }
     const uint64_t blk = rt::block_size(accel);
     const uint64_t lanes = uint64_t(ctx->cu_count) * ctx->occ[accel][ci][mode] * blk;
-    // Sample chunks per pixel (HASH only: the image does not depend on them):
-    // enough units for ~128 per lane, but units of at least 256 samples, so the frame is
-    // throughput-bound and its tail (the units running when the queue runs dry, about one unit
-    // long) short, without paying a unit's start and flush too often (config 3,
-    // 10 000 spp, 4 -> 25 chunks -2.0 %; config 5, 1000 spp 4K: 1 / 3 / 7 / 14 chunks 658.6 /
-    // 655.3 / 666.0 / 685.9 ms). Tuning sample_chunks forces a count, units_per_lane /
-    // unit_min_samples set the targets. The brute-force walk's samples cost ~n/10 times a grid
-    // sample, so its floor scales down with n (488 spheres: 5 samples; config 2, 100 spp: 1 -> 20
-    // chunks).
+    S.P = P;
+    S.accel = accel;
+    S.count = count;
+    S.flat = flat;
+    S.mode = mode;
+    S.ci = ci;
+    S.lds = lds;
+    S.blk = blk;
+    S.lanes = lanes;
+    S.tiles_x = tiles_x;
+    S.n_tiles = n_tiles;
+    return RT_OK;
+}
+
+// Sample chunks per pixel (HASH only: the image does not depend on them):
+// enough units for ~128 per lane, but units of at least 256 samples, so the frame is
+// throughput-bound and its tail (the units running when the queue runs dry, about one unit
+// long) short, without paying a unit's start and flush too often (config 3,
+// 10 000 spp, 4 -> 25 chunks -2.0 %; config 5, 1000 spp 4K: 1 / 3 / 7 / 14 chunks 658.6 /
+// 655.3 / 666.0 / 685.9 ms). Tuning sample_chunks forces a count, units_per_lane /
+// unit_min_samples set the targets. The brute-force walk's samples cost ~n/10 times a grid
+// sample, so its floor scales down with n (488 spheres: 5 samples; config 2, 100 spp: 1 -> 20
+// chunks).
+// `pixels` / `n_tiles`: the pixels and 8x8 tiles the launch hands out (the band's, or those of an
+// adaptive pass's tile list).
+uint64_t uniform_chunks(const rt_context* ctx, const TraceSetup& S, uint32_t spp, uint64_t pixels, uint64_t n_tiles,
+                        bool* forced) {
+    const rt::DeviceScene& d = ctx->scene;
+    const int mode = S.mode;
+    const uint32_t accel = S.accel;
+    const uint64_t lanes = S.lanes;
     uint64_t chunks = 1;
-    bool chunks_forced = false;
+    *forced = false;
     if (mode == rt::MODE_HASH && spp > 1) {
         // units of >= spp / 32 samples, between 32 and 128 (256 until round 5; 128 for every spp
         // until round 6): a band of the N = 8 frame (135 rows at 10 000 spp) is capped by this
@@ -1226,20 +1275,220 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         if (accel == rt::ACCEL_BRUTE) min_samples = std::min<uint64_t>(256, std::max<uint64_t>(4, 2560 / std::max(1u, d.n_spheres)));
         per_lane = std::max<uint64_t>(1, uint64_t(Tuning::get(ctx->tune.units_per_lane, double(per_lane))));
         min_samples = std::max<uint64_t>(1, uint64_t(Tuning::get(ctx->tune.unit_min_samples, double(min_samples))));
-        const uint64_t pixels = uint64_t(band_width) * band_height;
         chunks = std::min<uint64_t>((lanes * per_lane + pixels - 1) / pixels, std::max<uint64_t>(1, spp / min_samples));
         if (ctx->tune.sample_chunks != Tuning::kUnset) {
             chunks = uint64_t(ctx->tune.sample_chunks);
-            chunks_forced = true;
+            *forced = true;
         }
         chunks = std::max<uint64_t>(1, std::min<uint64_t>({chunks, spp, 4096}));
         while (chunks > 1 && n_tiles * chunks * 64u >= (1ull << 31)) chunks /= 2;   // unit ids in 32 bits
     }
+    return chunks;
+}
+
+// Issues one trace launch of S.P (its units, tile order and tables set by the caller): the grid,
+// the block hand-out, the prep kernel and the trace kernel between the launch's two timing events.
+int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
+    const rt::DeviceScene& d = ctx->scene;
+    rt::TraceParams& P = S.P;
+    const uint32_t accel = S.accel;
+    const bool count = S.count;
+    const int mode = S.mode, ci = S.ci;
+    const size_t lds = S.lds;
+    const uint64_t blk = S.blk, n_tiles = S.n_tiles;
+    const uint64_t full = uint64_t(ctx->cu_count) * ctx->occ[accel][ci][mode];
+    const uint64_t by_work = (uint64_t(P.n_units) + blk - 1) / blk;
+    const int grid = int(std::max<uint64_t>(1, std::min(full, by_work)));
+    {   // Block hand-out (DESIGN.md §4.1): the last `reserve` units go out one by one. Measured
+        // (scripts/refill_ab.py, 1080p): 0 to 32 Ki are within 1 %, one pixel per lane of the
+        // grid (262 Ki) is 10-15 % slower at 13-50 spp.
+        const uint64_t reserve = uint64_t(Tuning::get(ctx->tune.refill_reserve, 8192));
+        P.n_block_units = P.n_units > reserve ? uint32_t((P.n_units - reserve) & ~uint64_t(63)) : 0u;
+        P.first_blocks = uint32_t(std::min<uint64_t>(uint64_t(grid) * blk / 64u, P.n_block_units / 64u));
+        // A STREAM frame is as long as its longest pixel chain (DESIGN.md §4.1); the waves that
+        // start on the longest-chain tiles of the LPT order take no further work, so no refill of
+        // their other lanes slows the chain down. 1/512 of the waves (32 on a full MI355X):
+        // 12 spp -3.4 %, 50 spp -3 %, 100 spp +-0 (scripts/env_ab.py isolate_tiles). HASH
+        // units are short: no isolation.
+        const uint64_t iso = uint64_t(Tuning::get(ctx->tune.isolate_tiles, double(uint64_t(grid) * blk / 64u / 512u)));
+        P.isolate_blocks = (P.tile_order && mode == rt::MODE_STREAM) ? uint32_t(std::min<uint64_t>(P.first_blocks, iso)) : 0u;
+    }
+    if (accel == rt::ACCEL_LBVH_TOP && ctx->treelet_stale) {   // after a build, refit or re-pad
+        RT_HIP(rt::build_treelet(d.nodes, d.n_nodes, d.treelet, d.treelet_count, st));
+        ctx->treelet_stale = false;
+    }
+    hipEvent_t* kev = ctx->kev[ctx->kev_count % rt_context::kKernelEvents];
+    for (int k = 0; k < 2; k++)
+        if (!kev[k]) RT_HIP(hipEventCreate(&kev[k]));
+    // counters zeroed, work counter past the first blocks, big-sphere table, tile-cost table zeroed
+    RT_HIP(rt::launch_prep(P, P.first_blocks * 64u, ctx->big_tab, P.tile_cost ? uint32_t(n_tiles) : 0u, st));
+    P.big_tab = ctx->big_tab;
+    RT_HIP(hipEventRecord(kev[0], st));
+    RT_HIP(rt::launch_trace(P, accel, count, mode, grid, lds, st));
+    RT_HIP(hipEventRecord(kev[1], st));
+    ctx->kev_count++;
+    return RT_OK;
+}
+
+// Buffers of an adaptive frame of `texels` texels in `n_tiles` tiles. Growing frees the old ones
+// after the stream has drained (every earlier op of ctx is ordered before it).
+int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStream_t st) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    if (a.cap < texels) {
+        if (a.planes) {
+            RT_HIP(hipStreamSynchronize(st));
+            RT_HIP(hipFree(a.planes));
+        }
+        a.planes = nullptr;
+        a.cap = 0;
+        void* p = nullptr;
+        RT_HIP(hipMalloc(&p, texels * 6u * sizeof(unsigned long long)));
+        RT_HIP(hipMemsetAsync(p, 0, texels * 6u * sizeof(unsigned long long), st));
+        a.planes = static_cast<unsigned long long*>(p);
+        a.cap = texels;
+    }
+    if (a.cap_tiles < n_tiles) {
+        if (a.tiles) {
+            RT_HIP(hipStreamSynchronize(st));
+            RT_HIP(hipFree(a.tiles));
+        }
+        a.tiles = nullptr;
+        a.cap_tiles = 0;
+        void* p = nullptr;
+        RT_HIP(hipMalloc(&p, n_tiles * 4u * sizeof(uint32_t)));
+        a.tiles = static_cast<uint32_t*>(p);
+        a.cap_tiles = n_tiles;
+    }
+    if (!a.state) RT_HIP(hipMalloc(reinterpret_cast<void**>(&a.state), sizeof(rt::AdaptiveState)));
+    if (!a.host) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&a.host), sizeof(rt::AdaptiveState), hipHostMallocDefault));
+    if (!a.ev) RT_HIP(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
+    return RT_OK;
+}
+
+// The passes of an adaptive frame and its resolve. A failure after the first
+// launch leaves sums in the half-buffers: the caller clears them.
+int adaptive_passes(rt_context* ctx, TraceSetup& S, const rt_options& o, const rt_adaptive& ad, uint32_t max_spp,
+                    float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info, hipStream_t st) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    rt::TraceParams& P = S.P;
+    const uint64_t texels = uint64_t(P.band_w) * P.band_h, n_tiles = S.n_tiles;
+    unsigned long long* half[2] = {a.planes, a.planes + 3u * texels};
+    uint32_t* tile_n = a.tiles;
+    uint32_t* lists[2] = {a.tiles + n_tiles, a.tiles + 2u * n_tiles};
+    // the walk kernels record tile costs unconditionally (rt_kernels.hip record_tile_cost): a
+    // scratch table of the whole tile grid, never read
+    P.tile_cost = S.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * n_tiles : nullptr;
+    P.accumulate = 0u;
+    P.head_tiles = 0u;
+    RT_HIP(rt::launch_adaptive_init(a.state, st));
+    const uint32_t thr_q16 = rt::adaptive_thr_q16(ad.threshold);
+    uint32_t done = 0, passes = 0, cur = 0;
+    uint64_t active = n_tiles;
+    const uint32_t* list = nullptr;   // pass 0: every tile, row-major
+    while (active) {
+        const uint32_t k = passes == 0 ? ad.min_spp : std::min(ad.step_spp, max_spp - done);
+        for (uint32_t h = 0; h < 2; h++) {   // samples [done, done + k/2) into A, the next k/2 into B
+            P.spp = k / 2u;
+            P.sample_base = o.sample_base + done + h * (k / 2u);
+            P.fixed = half[h];
+            P.tile_order = list;
+            // uniform chunks by rt_render_device's rule for the pixels of the list; no head / tail
+            // split (the list carries no cost order)
+            bool forced = false;
+            const uint64_t chunks = uniform_chunks(ctx, S, P.spp, 64u * active, active, &forced);
+            if (active * chunks * 64u >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
+            P.chunks = uint32_t(chunks);
+            P.head_chunks = P.chunks;
+            P.n_units = uint32_t(active * chunks * 64u);
+            ctx->last_chunks = P.chunks;
+            if (int rc = launch_units(ctx, S, st)) return rc;
+        }
+        done += k;
+        rt::AdaptiveErrorParams K;
+        std::memset(&K, 0, sizeof(K));
+        K.a = half[0];
+        K.b = half[1];
+        K.texels = texels;
+        K.band_w = P.band_w;
+        K.band_h = P.band_h;
+        K.tiles_x = P.tiles_x;
+        K.list = list;
+        K.n_list = uint32_t(active);
+        K.n_done = done;
+        K.max_spp = max_spp;
+        K.thr_q16 = thr_q16;
+        K.cur = cur;
+        K.tile_n = tile_n;
+        K.next_list = lists[cur ^ 1u];
+        K.state = a.state;
+        RT_HIP(rt::launch_adaptive_error(K, st));
+        // the one host wait of the pass: the next list's length (and the running totals)
+        RT_HIP(hipMemcpyAsync(a.host, a.state, sizeof(rt::AdaptiveState), hipMemcpyDeviceToHost, st));
+        RT_HIP(hipEventRecord(a.ev, st));
+        RT_HIP(hipEventSynchronize(a.ev));
+        passes++;
+        cur ^= 1u;
+        active = a.host->count[cur];
+        list = lists[cur];
+        if (active > n_tiles) return fail(RT_ERR_DEVICE, "adaptive tile list longer than the tile grid");
+    }
+    RT_HIP(rt::launch_adaptive_resolve(half[0], half[1], texels, P.band_w, P.tiles_x, tile_n, accum, out, sample_count,
+                                       st));
+    if (info) {
+        info->passes = passes;
+        info->tiles = uint32_t(n_tiles);
+        info->tiles_capped = a.host->capped;
+        info->reserved = 0;
+        info->samples = a.host->samples;
+    }
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_set_scene(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream) {
+    return scene_call(ctx, spheres, count, false, stream, false);
+}
+
+int rt_set_scene_device(rt_context* ctx, const Sphere* d_spheres, uint32_t count, void* stream) {
+    return scene_call(ctx, d_spheres, count, true, stream, false);
+}
+
+int rt_refit_scene(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream) {
+    // without a device-built tree of this count there is no topology to reuse: a full build
+    return scene_call(ctx, spheres, count, false, stream, true);
+}
+
+int rt_refit_scene_device(rt_context* ctx, const Sphere* d_spheres, uint32_t count, void* stream) {
+    return scene_call(ctx, d_spheres, count, true, stream, true);
+}
+
+int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                     uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                     const rt_options* opt, void* stream) {
+    rt_options o;
+    bool empty = false;
+    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, "rt_render_device", o, &empty))
+        return rc;
+    if (empty) return RT_OK;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;
+    TraceSetup S;
+    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
+    rt::TraceParams& P = S.P;
+    const uint32_t accel = S.accel, spp = rci->samplesPerRenderCall;
+    const int mode = S.mode;
+    const uint64_t lanes = S.lanes, tiles_x = S.tiles_x, n_tiles = S.n_tiles;
+    bool chunks_forced = false;
+    uint64_t chunks = uniform_chunks(ctx, S, spp, uint64_t(band_width) * band_height, n_tiles, &chunks_forced);
     if (n_tiles * chunks * 64u >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
     P.chunks = uint32_t(chunks);
     ctx->last_accel = accel;
-    ctx->last_lds = lds;
-    ctx->last_flat = flat;
+    ctx->last_lds = S.lds;
+    ctx->last_flat = S.flat;
     ctx->last_pinhole = P.pinhole_lf != 0;
     const uint64_t texels = uint64_t(band_width) * band_height;
     if (mode == rt::MODE_HASH) {
@@ -1314,37 +1563,7 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         sc.rec_head_chunks[sc.cur] = P.head_chunks;
         sc.rec_chunks[sc.cur] = P.chunks;
     }
-    const uint64_t full = uint64_t(ctx->cu_count) * ctx->occ[accel][ci][mode];
-    const uint64_t by_work = (uint64_t(P.n_units) + blk - 1) / blk;
-    const int grid = int(std::max<uint64_t>(1, std::min(full, by_work)));
-    {   // Block hand-out (DESIGN.md §4.1): the last `reserve` units go out one by one. Measured
-        // (scripts/refill_ab.py, 1080p): 0 to 32 Ki are within 1 %, one pixel per lane of the
-        // grid (262 Ki) is 10-15 % slower at 13-50 spp.
-        const uint64_t reserve = uint64_t(Tuning::get(ctx->tune.refill_reserve, 8192));
-        P.n_block_units = P.n_units > reserve ? uint32_t((P.n_units - reserve) & ~uint64_t(63)) : 0u;
-        P.first_blocks = uint32_t(std::min<uint64_t>(uint64_t(grid) * blk / 64u, P.n_block_units / 64u));
-        // A STREAM frame is as long as its longest pixel chain (DESIGN.md §4.1); the waves that
-        // start on the longest-chain tiles of the LPT order take no further work, so no refill of
-        // their other lanes slows the chain down. 1/512 of the waves (32 on a full MI355X):
-        // 12 spp -3.4 %, 50 spp -3 %, 100 spp +-0 (scripts/env_ab.py isolate_tiles). HASH
-        // units are short: no isolation.
-        const uint64_t iso = uint64_t(Tuning::get(ctx->tune.isolate_tiles, double(uint64_t(grid) * blk / 64u / 512u)));
-        P.isolate_blocks = (P.tile_order && mode == rt::MODE_STREAM) ? uint32_t(std::min<uint64_t>(P.first_blocks, iso)) : 0u;
-    }
-    if (accel == rt::ACCEL_LBVH_TOP && ctx->treelet_stale) {   // after a build, refit or re-pad
-        RT_HIP(rt::build_treelet(d.nodes, d.n_nodes, d.treelet, d.treelet_count, st));
-        ctx->treelet_stale = false;
-    }
-    hipEvent_t* kev = ctx->kev[ctx->kev_count % rt_context::kKernelEvents];
-    for (int k = 0; k < 2; k++)
-        if (!kev[k]) RT_HIP(hipEventCreate(&kev[k]));
-    // counters zeroed, work counter past the first blocks, big-sphere table, tile-cost table zeroed
-    RT_HIP(rt::launch_prep(P, P.first_blocks * 64u, ctx->big_tab, P.tile_cost ? uint32_t(n_tiles) : 0u, st));
-    P.big_tab = ctx->big_tab;
-    RT_HIP(hipEventRecord(kev[0], st));
-    RT_HIP(rt::launch_trace(P, accel, count, mode, grid, lds, st));
-    RT_HIP(hipEventRecord(kev[1], st));
-    ctx->kev_count++;
+    if (int rc = launch_units(ctx, S, st)) return rc;
     if (mode == rt::MODE_HASH)
         RT_HIP(rt::launch_resolve_fixed(ctx->fixed, texels, P.accumulate, spp, accum, out, st));
     if (P.tile_cost && ctx->keep_snaps) {   // this launch's record (+ its order) for rt_launch_row_weights
@@ -1384,6 +1603,68 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         sl.used = true;
     }
     return mark_issued(ctx, st);
+}
+
+int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                              uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                              uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
+                              rt_adaptive_info* info, void* stream) {
+    if (info) std::memset(info, 0, sizeof(*info));
+    rt_options o;
+    bool empty = false;
+    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, "rt_render_adaptive_device", o,
+                                   &empty))
+        return rc;
+    if (empty) return RT_OK;
+    if (!ad) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive is NULL");
+    const uint32_t max_spp = rci->samplesPerRenderCall;
+    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_device needs rng_mode RT_RNG_SAMPLE_HASH");
+    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_device: accumulate must be 0");
+    if (ad->min_spp == 0 || (ad->min_spp & 1u)) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp must be even and >= 2");
+    if (ad->step_spp == 0 || (ad->step_spp & 1u))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive step_spp must be even and >= 2");
+    if (max_spp == 0 || (max_spp & 1u))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive max_spp (samplesPerRenderCall) must be even and >= 2");
+    if (ad->min_spp > max_spp) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp exceeds max_spp (samplesPerRenderCall)");
+    if (uint64_t(o.sample_base) + max_spp > 0xffffffffull)
+        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + max_spp overflows 32 bits");
+    if (!(std::isfinite(ad->threshold) && ad->threshold >= 0.0f && ad->threshold <= 16.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive threshold must be finite and within [0, 16]");
+    if (ad->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive reserved must be 0");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;
+    TraceSetup S;
+    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
+    if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, S.n_tiles, st)) return rc;
+    ctx->last_accel = S.accel;
+    ctx->last_lds = S.lds;
+    ctx->last_flat = S.flat;
+    ctx->last_pinhole = S.P.pinhole_lf != 0;
+    int rc = adaptive_passes(ctx, S, o, *ad, max_spp, accum, out, sample_count, info, st);
+    if (rc != RT_OK) {   // the half-buffers are zero between calls, whatever happened
+        const std::string msg = rt::g_last_error;
+        (void)hipMemsetAsync(ctx->adaptive.planes, 0, ctx->adaptive.cap * 6u * sizeof(unsigned long long), st);
+        rt::g_last_error = msg;
+    }
+    if (ctx->slot_cur >= 0) {   // the next build into this arena waits for these launches
+        SceneSlot& sl = ctx->slot[ctx->slot_cur];
+        RT_HIP(hipEventRecord(sl.ev_free, st));
+        sl.used = true;
+    }
+    if (int rc2 = mark_issued(ctx, st)) return rc ? rc : rc2;
+    return rc;
+}
+
+int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, int* converged) {
+    if (!converged) return fail(RT_ERR_INVALID_ARGUMENT, "converged is NULL");
+    if (E >= rt::kAdaptiveMaxSum || S >= rt::kAdaptiveMaxSum)
+        return fail(RT_ERR_INVALID_ARGUMENT, "E and S must be below 2^56");
+    if (n > rt::kAdaptiveMaxSpp) return fail(RT_ERR_INVALID_ARGUMENT, "n above 2^19");
+    if (m == 0 || m > 64u) return fail(RT_ERR_INVALID_ARGUMENT, "m must be within 1 .. 64");
+    *converged = rt::adaptive_tile_converged(E, S, n, m, thr_q16) ? 1 : 0;
+    return RT_OK;
 }
 
 int rt_get_stats(rt_context* ctx, rt_stats* out) {

@@ -13,6 +13,9 @@
 //   frame k renders.
 //   --rng stream|hash: the reference's per-pixel LCG stream (default) or the counter-based
 //   RT_RNG_SAMPLE_HASH stream, for --frames and for the single ray_trace() frame alike.
+//   --adaptive THRESHOLD[,MIN[,STEP]]: one adaptive frame (rt_render_adaptive_device) on one GPU
+//   in the counter-based stream: MIN samples everywhere (default 16), STEP more per pass (default
+//   MIN) on the 8x8 tiles noisier than THRESHOLD, at most --samples per pixel.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -120,12 +123,76 @@ int run_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t gpu_c
     return 0;
 }
 
+// One adaptive frame of the canonical scene on device 0.
+int run_adaptive(uint32_t samples, uint32_t width, uint32_t height, bool store, const rt_adaptive& ad) {
+    rt_context* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    float* accum = nullptr;
+    uint8_t* rgba8 = nullptr;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    CLI_HIP(hipMalloc(&accum, size_t(width) * height * 16));
+    CLI_HIP(hipMalloc(&rgba8, size_t(width) * height * 4));
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0;
+    CLI_RT(rt_generate_scene(0.0f, 11, scene.data(), uint32_t(scene.size()), &cnt));
+    CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+    RenderCallInfo rci;
+    CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+    rt_options opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    rt_adaptive_info info;
+    CLI_HIP(hipStreamSynchronize(stream));
+    const auto b = std::chrono::steady_clock::now();
+    CLI_RT(rt_render_adaptive_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, &ad, &info, stream));
+    CLI_HIP(hipStreamSynchronize(stream));
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+    const double pixels = double(width) * height;
+    std::printf("duration_per_frame: %.3f ms (adaptive, threshold %g: %u passes, mean %.2f spp of at most %u, "
+                "%u of %u tiles capped, %.1f Msamples/s)\n",
+                sec * 1e3, double(ad.threshold), info.passes, double(info.samples) / pixels, samples, info.tiles_capped,
+                info.tiles, double(info.samples) / sec / 1e6);
+    if (store) {
+        std::vector<uint8_t> img(size_t(width) * height * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    (void)hipFree(accum);
+    (void)hipFree(rgba8);
+    return 0;
+}
+
+// THRESHOLD[,MIN[,STEP]]
+bool parse_adaptive(const char* s, rt_adaptive& ad) {
+    std::memset(&ad, 0, sizeof(ad));
+    char* end = nullptr;
+    ad.threshold = std::strtof(s, &end);
+    if (end == s) return false;
+    ad.min_spp = 16;
+    if (*end == ',') {
+        const std::string rest = end + 1;
+        const size_t comma = rest.find(',');
+        if (!parse_u32(rest.substr(0, comma).c_str(), ad.min_spp)) return false;
+        ad.step_spp = ad.min_spp;
+        if (comma != std::string::npos && !parse_u32(rest.c_str() + comma + 1, ad.step_spp)) return false;
+        return true;
+    }
+    ad.step_spp = ad.min_spp;
+    return *end == '\0';
+}
+
 }  // namespace
 
 int main(int argc, const char** argv) {
     uint32_t samples = 10, width = 1920, height = 1080, gpu_count = 1, frames = 0, rng_mode = RT_RNG_PIXEL_STREAM;
     bool rng_explicit = false;
-    bool store = false, animate = false;
+    bool store = false, animate = false, adaptive = false;
+    rt_adaptive ad;
+    std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--help") {
@@ -138,7 +205,16 @@ int main(int argc, const char** argv) {
             std::puts("--frames <count>                  # Benchmark loop: render count frames, print duration_per_frame");
             std::puts("--animate                         # With --frames: scene time t = seconds since start");
             std::puts("--rng <stream|hash>               # Reference per-pixel LCG stream (default) or counter-based stream");
+            std::puts("--adaptive <thr>[,<min>[,<step>]] # One GPU, hash stream: min spp everywhere, step more per pass on");
+            std::puts("                                  # tiles noisier than thr, at most --samples per pixel");
             return 0;
+        } else if (a == "--adaptive") {
+            if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
+                std::fprintf(stderr, "--adaptive needs THRESHOLD[,MIN[,STEP]]\n");
+                return 2;
+            }
+            ++i;
+            adaptive = true;
         } else if (a == "--store") {
             store = true;
         } else if (a == "--animate") {
@@ -166,11 +242,26 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "unknown argument: %s\n", argv[i]);
         }
     }
+    if (adaptive) {   // refused before anything renders
+        if (rng_explicit && rng_mode != RT_RNG_SAMPLE_HASH) {
+            std::fprintf(stderr, "--adaptive needs the counter-based stream: it cannot run with --rng stream\n");
+            return 2;
+        }
+        if (gpu_count > 1) {
+            std::fprintf(stderr, "--adaptive renders on one GPU: it cannot run with --gpus %u\n", gpu_count);
+            return 2;
+        }
+        if (frames > 0) {
+            std::fprintf(stderr, "--adaptive renders one frame: it cannot run with --frames\n");
+            return 2;
+        }
+    }
     int n = 0;
     if (rt_device_count(&n) != RT_OK) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
+    if (adaptive) return run_adaptive(samples, width, height, store, ad);
     if (frames > 0) return run_frames(samples, width, height, gpu_count, frames, animate, store, rng_mode);
     // ray_trace() keeps the reference's signature; its stream is selected through RT_RNG. An
     // explicit --rng wins over the caller's environment; without it RT_RNG passes through.

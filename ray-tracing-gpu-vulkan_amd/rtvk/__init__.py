@@ -19,14 +19,15 @@ from typing import Iterable, Optional, Sequence
 import numpy as np
 
 from . import abi
-from .abi import (CHECKERED, DIFFUSE, METAL, REFRACTIVE, SOLID, Options, RenderCallInfo, RtError,
-                  Scene, Sphere, Stats, check, load_library)
+from .abi import (CHECKERED, DIFFUSE, METAL, REFRACTIVE, SOLID, Adaptive, AdaptiveInfo, Options, RenderCallInfo,
+                  RtError, Scene, Sphere, Stats, check, load_library)
 
 __all__ = [
     "DIFFUSE", "METAL", "REFRACTIVE", "SOLID", "CHECKERED", "Sphere", "Scene", "RenderCallInfo",
     "Options", "Stats", "RtError", "generateRandomScene", "canonical_render_call_info",
     "make_options", "Renderer", "MultiRenderer", "render", "ray_trace", "store_ppm", "spheres_to_numpy",
     "load_library", "HASH", "STREAM", "multi_plan", "partition_strips", "partition_rebalance",
+    "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -68,6 +69,28 @@ def make_options(max_depth: int = MAX_DEPTH, seed_mode: int = abi.RT_SEED_GLOBAL
     o.accumulate, o.sample_base = int(bool(accumulate)), sample_base
     o.reserved[0] = 1 if count_tests else 0
     return o
+
+
+def make_adaptive(threshold: float, min_spp: int = 8, step_spp: int = 8) -> Adaptive:
+    """rt_adaptive of an adaptive frame (Renderer.render_adaptive): every pixel gets `min_spp`
+    samples, tiles that have not converged to `threshold` get `step_spp` more per pass, up to the
+    RenderCallInfo's samplesPerRenderCall. Counts are even, 0 <= threshold <= 16."""
+    a = Adaptive()
+    a.min_spp, a.step_spp, a.threshold, a.reserved = min_spp, step_spp, threshold, 0
+    return a
+
+
+def threshold_q16(threshold: float) -> int:
+    """The criterion's integer threshold: floor(double(float32(threshold)) * 65536 + 0.5)."""
+    return int(np.floor(float(np.float32(threshold)) * 65536.0 + 0.5))
+
+
+def adaptive_tile_converged(E: int, S: int, n: int, m: int, thr_q16: int) -> bool:
+    """The stop criterion of one tile as the library evaluates it (rt_adaptive_tile_converged,
+    host only): 2^17 E < thr_q16 (S + n * 3 * m * 2^16)."""
+    c = ctypes.c_int(0)
+    check(load_library().rt_adaptive_tile_converged(E, S, n, m, thr_q16, ctypes.byref(c)))
+    return bool(c.value)
 
 
 def _stream_ptr(stream, device: int) -> Optional[int]:
@@ -211,6 +234,38 @@ class Renderer:
                                          accum.data_ptr(), out.data_ptr(),
                                          ctypes.byref(options) if options is not None else None,
                                          _stream_ptr(stream, self.device)))
+
+    def render_adaptive(self, rci: RenderCallInfo, accum, out, sample_count=None, rows=None,
+                        options: Optional[Options] = None, adaptive: Optional[Adaptive] = None,
+                        stream=None) -> AdaptiveInfo:
+        """One band rendered to a noise level (rt_render_adaptive_device): `adaptive` from
+        make_adaptive(), rci.samplesPerRenderCall the cap, options with rng_mode HASH. Tensors as
+        render_device; sample_count: optional 4-byte integer cuda tensor [band_h, band_w] that
+        receives each texel's sample count. Ordered on `stream`, but blocks the host once per pass;
+        the outputs are valid once `stream` completes. Returns the frame's AdaptiveInfo."""
+        if adaptive is None:
+            raise ValueError("adaptive is required (make_adaptive)")
+        bh, bw = int(accum.shape[0]), int(accum.shape[1])
+        _check_dev_tensor(accum, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        rows_ptr = None
+        if rows is not None:
+            if rows.numel() != bh or not rows.is_cuda or rows.element_size() != 4 or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous 4-byte cuda tensor of band_h entries")
+            rows_ptr = rows.data_ptr()
+        count_ptr = None
+        if sample_count is not None:
+            if not sample_count.is_cuda or sample_count.element_size() != 4 or sample_count.is_floating_point() \
+                    or not sample_count.is_contiguous() or tuple(sample_count.shape) != (bh, bw):
+                raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            count_ptr = sample_count.data_ptr()
+        info = AdaptiveInfo()
+        check(self._lib.rt_render_adaptive_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
+                                                  accum.data_ptr(), out.data_ptr(), count_ptr,
+                                                  ctypes.byref(options) if options is not None else None,
+                                                  ctypes.byref(adaptive), ctypes.byref(info),
+                                                  _stream_ptr(stream, self.device)))
+        return info
 
     def stats(self) -> Stats:
         st = Stats()

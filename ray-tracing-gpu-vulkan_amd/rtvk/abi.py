@@ -88,10 +88,23 @@ class Stats(ctypes.Structure):
                 ("box_tests", ctypes.c_uint64), ("sphere_tests", ctypes.c_uint64)]
 
 
+class Adaptive(ctypes.Structure):
+    """rt_adaptive (include/rt_mi355x.h)."""
+    _fields_ = [("min_spp", ctypes.c_uint32), ("step_spp", ctypes.c_uint32), ("threshold", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
+class AdaptiveInfo(ctypes.Structure):
+    """rt_adaptive_info (include/rt_mi355x.h)."""
+    _fields_ = [("passes", ctypes.c_uint32), ("tiles", ctypes.c_uint32), ("tiles_capped", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("samples", ctypes.c_uint64)]
+
+
 assert ctypes.sizeof(Sphere) == 80 and Sphere.materialSpecificAttribute.offset == 64
 assert ctypes.sizeof(Scene) == 41024 and Scene.sphereAmount.offset == 40960
 assert ctypes.sizeof(RenderCallInfo) == 64 and RenderCallInfo.camera_dir.offset == 48
 assert ctypes.sizeof(Options) == 32
+assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and AdaptiveInfo.samples.offset == 16
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
 _P, _U32, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
@@ -109,6 +122,10 @@ EXPORTS = {
     "rt_refit_scene_device": (_I, [_P, _P, _U32, _P]),
     "rt_render_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P,
                               ctypes.POINTER(Options), _P]),
+    "rt_render_adaptive_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
+                                       ctypes.POINTER(Options), ctypes.POINTER(Adaptive),
+                                       ctypes.POINTER(AdaptiveInfo), _P]),
+    "rt_adaptive_tile_converged": (_I, [ctypes.c_uint64, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(_I)]),
     "rt_get_stats": (_I, [_P, ctypes.POINTER(Stats)]),
     "rt_launch_ms": (_I, [_P, _U32, ctypes.POINTER(ctypes.c_float)]),
     "rt_launch_row_weights": (_I, [_P, _U32, _P, _U32]),
