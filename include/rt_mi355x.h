@@ -156,7 +156,12 @@ int rt_context_destroy(rt_context* ctx);
  * the context's own build stream into the one of two scene arenas that no queued launch reads
  * (the one used two scenes ago, whose launches they wait for), so frame k + 1's build overlaps
  * frame k's tail; the call returns once the build's summary is back on the host (no wait for
- * queued launches) and its grid build is queued. */
+ * queued launches) and its grid build is queued.
+ * Geometry: finite centres and radii of any sign or size are rendered as the CPU
+ * oracle renders them (radius -r is the sphere of radius r, radius 0 is never hit, of coincident
+ * spheres the lowest index wins). A sphere with a NaN or infinite centre or radius is refused:
+ * RT_ERR_INVALID_ARGUMENT, rt_last_error() names the first such index, and ctx keeps the scene it
+ * had. This holds for every scene call below, rt_multi_set_scene and ray_trace() alike. */
 int rt_set_scene(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream);
 /* As rt_set_scene, spheres already in DEVICE memory, written by earlier work on `stream` (the
  * build copies them after that work; the caller may reuse them once the call returns). */

@@ -106,6 +106,8 @@ struct rt_context {
     bool pending = false;                        // a build begun, not yet ended (rt_multi_set_scene)
     int pending_slot = 0;
     uint32_t pending_count = 0;
+    bool refused = false;                        // device_build_end refused non-finite device spheres:
+                                                 // the scene call leaves the previous scene in place
     rt::Counters* counters = nullptr;            // device
     float* big_tab = nullptr;                    // device, in the counters' allocation (TraceParams::big_tab)
     // Every device operation of a context (scene upload / build, render) is ordered after the
@@ -451,6 +453,11 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+int refuse_nonfinite(uint32_t index) {
+    return fail(RT_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(index) +
+                                             ": centre or radius is not finite (NaN or inf); the scene is refused");
+}
+
 int current_device_count(int* n) {
     hipError_t e = hipGetDeviceCount(n);
     if (e != hipSuccess || *n <= 0) {
@@ -462,6 +469,7 @@ int current_device_count(int* n) {
 }  // namespace rt
 
 using rt::fail;
+using rt::refuse_nonfinite;
 using rt::DeviceGuard;
 
 extern "C" {
@@ -843,6 +851,17 @@ int device_build_end(rt_context* ctx) {
     const hipStream_t bs = ctx->build_stream;
     RT_HIP(hipEventSynchronize(ctx->ev_summary));
     const rt::BuildSummary sm = *ctx->summary;
+    if (sm.first_nonfinite != 0xffffffffu) {
+        // The geometry contract, device-resident spheres: k_prep found a NaN / inf
+        // centre or radius. The build kernels have ended (their loops are bounded by the integer
+        // tree structure, never by a float comparison); the arena they wrote is not the current
+        // scene's, no grid is built over it and no launch will read it. The stored topology is the
+        // refused scene's, so the next refit is a full build.
+        ctx->refused = true;
+        ctx->topo_ok = false;
+        ctx->ws.topo_n = 0;
+        return refuse_nonfinite(sm.first_nonfinite);
+    }
     rt::DeviceScene& d = s.scene;
     d.n_spheres = ctx->pending_count;
     d.n_big = sm.n_big;
@@ -909,10 +928,17 @@ Builder pick_builder(uint32_t count) {
     return count <= kHostSahMaxSpheres ? Builder::HOST_SAH : Builder::GPU;
 }
 
-int check_scene_args(rt_context* ctx, const Sphere* spheres, uint32_t count) {
+// Host spheres are checked against the geometry contract here, before any builder
+// sees them and with the context untouched; device-resident ones by the build's k_prep, refused in
+// device_build_end.
+int check_scene_args(rt_context* ctx, const Sphere* spheres, uint32_t count, bool device_ptr) {
     if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
     if (!spheres && count) return fail(RT_ERR_INVALID_ARGUMENT, "spheres is NULL");
     if (count >= (1u << 27)) return fail(RT_ERR_INVALID_ARGUMENT, "too many spheres");
+    if (!device_ptr) {
+        const uint32_t bad = rt::first_nonfinite_geometry(spheres, count);
+        if (bad < count) return refuse_nonfinite(bad);
+    }
     return RT_OK;
 }
 
@@ -960,7 +986,7 @@ int scene_end(rt_context* ctx) {
 
 namespace rt {
 int set_scene_begin(rt_context* ctx, const Sphere* spheres, uint32_t count, void* stream, HostPackagePtr* shared) {
-    if (int rc = check_scene_args(ctx, spheres, count)) return rc;
+    if (int rc = check_scene_args(ctx, spheres, count, false)) return rc;
     const int rc = scene_begin(ctx, spheres, count, false, static_cast<hipStream_t>(stream), false, shared);
     if (rc != RT_OK) {
         ctx->pending = false;
@@ -972,6 +998,10 @@ int set_scene_begin(rt_context* ctx, const Sphere* spheres, uint32_t count, void
 int set_scene_end(rt_context* ctx) {
     const int rc = scene_end(ctx);
     ctx->pending = false;
+    if (ctx->refused) {   // (host spheres are refused in set_scene_begin; kept for symmetry with scene_call)
+        ctx->refused = false;
+        return rc;
+    }
     return scene_done(ctx, rc);
 }
 }  // namespace rt
@@ -979,10 +1009,14 @@ int set_scene_end(rt_context* ctx) {
 namespace {
 
 int scene_call(rt_context* ctx, const Sphere* spheres, uint32_t count, bool device_ptr, void* stream, bool refit) {
-    if (int rc = check_scene_args(ctx, spheres, count)) return rc;
+    if (int rc = check_scene_args(ctx, spheres, count, device_ptr)) return rc;
     int rc = scene_begin(ctx, spheres, count, device_ptr, static_cast<hipStream_t>(stream), refit, nullptr);
     if (rc == RT_OK) rc = scene_end(ctx);
     ctx->pending = false;
+    if (ctx->refused) {   // non-finite device spheres: the previous scene stands as it was
+        ctx->refused = false;
+        return rc;
+    }
     return scene_done(ctx, rc);
 }
 

@@ -18,6 +18,8 @@ struct BuildSummary {
     uint32_t rmin_o;                 // ... and of the smallest small radius
     uint32_t cmin_o[3], cmax_o[3];   // centroid bounds of the small spheres (Morton frame)
     uint32_t colour_out_of_range;    // != 0: some sphere colour leaves [0, 1] (colours_in_unit)
+    uint32_t first_nonfinite;        // lowest index of a sphere with a NaN / inf centre or radius
+                                     // (0xffffffff: none): the host refuses the scene
     float root_lo[3], root_hi[3];    // unpadded root box (the small spheres' AABB union): the grid's
                                      // bounds, so the host needs no second read-back
 };

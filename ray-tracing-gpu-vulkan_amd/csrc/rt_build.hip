@@ -7,7 +7,7 @@
 //
 //   prep      Sphere (80-B std140, HBM) -> GeomRec / radius / MatRec records, brute-force pad
 //             records, scene radius R (max |center| + |r|, exact max via ordered-int atomics)
-//   sort 1    radii, descending, stable (hipCUB radix sort): median and the 64 largest "big"
+//   sort 1    |radii|, descending, stable (hipCUB radix sort): median and the 64 largest "big"
 //             spheres with the host's tie order (stable_sort by radius over index order)
 //   select    one wave: threshold 2 x median, big ids ascending, is_big flags
 //   reduce    centroid bounds and largest radius of the small spheres
@@ -91,6 +91,7 @@ __global__ void k_init(BuildSummary* S, bool refit) {
     S->rmax_o = f2o(0.0f);
     S->rmin_o = f2o(INFINITY);
     S->colour_out_of_range = 0u;
+    S->first_nonfinite = kEnd;
     S->R_o = f2o(0.0f);
 }
 
@@ -107,8 +108,11 @@ __global__ void __launch_bounds__(kBlock) k_prep(const Sphere* __restrict__ sph,
         radius[i] = r;
         mat[i] = make_mat(s.colors[0].x, s.colors[0].y, s.colors[0].z, s.materialSpecificAttribute,
                           s.colors[1].x, s.colors[1].y, s.colors[1].z, s.materialType, s.textureType);
-        if (rkeys) { rkeys[i] = r; ids[i] = i; }
+        if (rkeys) { rkeys[i] = __builtin_fabsf(r); ids[i] = i; }   // size, whatever the sign (rt_bvh.cpp)
         if (!colours_in_unit(s)) atomicOr(&S->colour_out_of_range, 1u);
+        // the geometry contract (rt_grid.h first_nonfinite_geometry): the host refuses the scene
+        if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && __builtin_isfinite(r)))
+            atomicMin(&S->first_nonfinite, i);
         Ro = f2o(__builtin_sqrtf(x * x + y * y + z * z) + __builtin_fabsf(r));
     } else if (i < n_geom) {   // brute-force pad record: never hit (rt_api.cpp)
         geom[i] = GeomRec{0.0f, 1e19f, 0.0f, -1e38f};
@@ -155,8 +159,8 @@ __global__ void __launch_bounds__(kBlock) k_reduce(const Sphere* __restrict__ sp
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         if (is_big[i]) continue;
         const rt_vec4 g = sph[i].geometry;
-        rmax = max(rmax, f2o(g.w));
-        rmin = min(rmin, f2o(g.w));
+        rmax = max(rmax, f2o(__builtin_fabsf(g.w)));
+        rmin = min(rmin, f2o(__builtin_fabsf(g.w)));
         const float c[3] = {g.x, g.y, g.z};
 #pragma unroll
         for (int k = 0; k < 3; k++) { cmin[k] = min(cmin[k], f2o(c[k])); cmax[k] = max(cmax[k], f2o(c[k])); }
@@ -249,8 +253,9 @@ __global__ void __launch_bounds__(kBlock) k_karras(const uint32_t* __restrict__ 
 
 __device__ __forceinline__ void prim_box(const Sphere* __restrict__ sph, uint32_t id, float* b) {
     const rt_vec4 g = sph[id].geometry;
-    b[0] = g.x - g.w; b[1] = g.y - g.w; b[2] = g.z - g.w;   // the sphere's AABB as the
-    b[3] = g.x + g.w; b[4] = g.y + g.w; b[5] = g.z + g.w;   // traversal's gate computes it
+    const float r = __builtin_fabsf(g.w);                // the gate's box is the same for r and -r
+    b[0] = g.x - r; b[1] = g.y - r; b[2] = g.z - r;   // the sphere's AABB as the
+    b[3] = g.x + r; b[4] = g.y + r; b[5] = g.z + r;   // traversal's gate computes it
 }
 
 // Box pyramid over the m sorted spheres: level 0 = each sphere's box (lo.w = 1 when the sphere is
@@ -548,9 +553,10 @@ __global__ void __launch_bounds__(kBlock) k_grid_refs(const Sphere* __restrict__
     if (i >= n || is_big[i]) return;
     const rt_vec4 s = sph[i].geometry;
     uint32_t a[3], b[3];
-    grid_range(g, 0, s.x, s.w, a[0], b[0]);
-    grid_range(g, 1, s.y, s.w, a[1], b[1]);
-    grid_range(g, 2, s.z, s.w, a[2], b[2]);
+    const float r = __builtin_fabsf(s.w);
+    grid_range(g, 0, s.x, r, a[0], b[0]);
+    grid_range(g, 1, s.y, r, a[1], b[1]);
+    grid_range(g, 2, s.z, r, a[2], b[2]);
     for (uint32_t z = a[2]; z <= b[2]; z++)
         for (uint32_t y = a[1]; y <= b[1]; y++)
             for (uint32_t x = a[0]; x <= b[0]; x++) {

@@ -5,7 +5,7 @@
 // walk needs no stack: hit inner node -> index + 1, miss or leaf done -> escape.
 //
 // Construction (Karras-style binary radix tree over Morton codes):
-//   1. "big" spheres (radius > 2 x median radius; at most 64, largest first) are kept out of the
+//   1. "big" spheres (|radius| > 2 x median |radius|; at most 64, largest first) are kept out of the
 //      tree and tested exhaustively: the reference ground sphere (r = 1000) would otherwise
 //      inflate every ancestor box up to the root.
 //   2. small-sphere centers quantised to 10 bits per axis inside their bounds, 30-bit Morton
@@ -14,7 +14,7 @@
 //      binary radix tree of Karras 2012, which rt_build.hip constructs in parallel — cut
 //      at subtrees of at most kLeafMax spheres, which become leaves stored in kLeafMax slots
 //      (dummy-padded) so the device issues a leaf's four loads together.
-//   4. node bounds = exact float min/max of the member spheres' AABBs (center -/+ radius), so
+//   4. node bounds = exact float min/max of the member spheres' AABBs (center -/+ |radius|), so
 //      every node box contains its spheres' AABBs bit-exactly (the traversal's exactness
 //      argument, DESIGN.md §4.3, needs this).
 #include <algorithm>
@@ -68,9 +68,10 @@ struct Builder {
         for (uint32_t i = lo; i < hi; i++) {
             const rt_vec4& g = sph[prims[i].id].geometry;
             const float c[3] = {g.x, g.y, g.z};
+            const float r = std::fabs(g.w);   // the gate's box is the same for r and -r
             for (int k = 0; k < 3; k++) {
-                bmin[k] = std::min(bmin[k], c[k] - g.w);   // the sphere's AABB, exactly as the
-                bmax[k] = std::max(bmax[k], c[k] + g.w);   // traversal test computes it
+                bmin[k] = std::min(bmin[k], c[k] - r);   // the sphere's AABB, exactly as the
+                bmax[k] = std::max(bmax[k], c[k] + r);   // traversal test computes it
             }
         }
     }
@@ -116,15 +117,15 @@ struct Builder {
             float rl[3] = {INFINITY, INFINITY, INFINITY}, rh[3] = {-INFINITY, -INFINITY, -INFINITY};
             for (uint32_t i = n; i-- > 1;) {
                 const rt_vec4& g = sph[tmp[i].id].geometry;
-                const float c[3] = {g.x, g.y, g.z};
-                for (int j = 0; j < 3; j++) { rl[j] = std::min(rl[j], c[j] - g.w); rh[j] = std::max(rh[j], c[j] + g.w); }
+                const float c[3] = {g.x, g.y, g.z}, r = std::fabs(g.w);
+                for (int j = 0; j < 3; j++) { rl[j] = std::min(rl[j], c[j] - r); rh[j] = std::max(rh[j], c[j] + r); }
                 right[i] = area(rl, rh);
             }
             float ll[3] = {INFINITY, INFINITY, INFINITY}, lh[3] = {-INFINITY, -INFINITY, -INFINITY};
             for (uint32_t i = 0; i + 1 < n; i++) {   // left = [0, i], right = [i + 1, n)
                 const rt_vec4& g = sph[tmp[i].id].geometry;
-                const float c[3] = {g.x, g.y, g.z};
-                for (int j = 0; j < 3; j++) { ll[j] = std::min(ll[j], c[j] - g.w); lh[j] = std::max(lh[j], c[j] + g.w); }
+                const float c[3] = {g.x, g.y, g.z}, r = std::fabs(g.w);
+                for (int j = 0; j < 3; j++) { ll[j] = std::min(ll[j], c[j] - r); lh[j] = std::max(lh[j], c[j] + r); }
                 const uint32_t nl = i + 1, nr = n - nl;
                 const double cost = knobs.classic ? area(ll, lh) * nl + right[i + 1] * nr
                                                   : area(ll, lh) * ((nl + kLeafMax - 1) / kLeafMax) +
@@ -159,9 +160,10 @@ struct Builder {
             return ex * ey + ey * ez + ez * ex;
         };
         auto bin_of = [&](int k, float c) {
+            // clamped before the cast: an extent that overflows to inf makes the quotient NaN
             const float ext = cmax[k] - cmin[k];
-            int b = int(double(c - cmin[k]) / ext * kBins);
-            return std::min(std::max(b, 0), kBins - 1);
+            const double b = double(c - cmin[k]) / ext * kBins;
+            return !(b > 0.0) ? 0 : b >= double(kBins - 1) ? kBins - 1 : int(b);
         };
         double best_cost = INFINITY;
         int best_axis = -1, best_plane = 0;
@@ -173,12 +175,12 @@ struct Builder {
                 for (int j = 0; j < 3; j++) { bl[b][j] = INFINITY; bh[b][j] = -INFINITY; }
             for (uint32_t i = lo; i < hi; i++) {
                 const rt_vec4& g = sph[prims[i].id].geometry;
-                const float c[3] = {g.x, g.y, g.z};
+                const float c[3] = {g.x, g.y, g.z}, r = std::fabs(g.w);
                 const int b = bin_of(k, c[k]);
                 cnt[b]++;
                 for (int j = 0; j < 3; j++) {
-                    bl[b][j] = std::min(bl[b][j], c[j] - g.w);
-                    bh[b][j] = std::max(bh[b][j], c[j] + g.w);
+                    bl[b][j] = std::min(bl[b][j], c[j] - r);
+                    bh[b][j] = std::max(bh[b][j], c[j] + r);
                 }
             }
             double right_area[kBins];
@@ -271,7 +273,7 @@ void build_lbvh_host(const Sphere* sph, uint32_t n, HostBvh& out, bool sah, uint
     if (n >= (1u << 27)) return;   // leaf references hold 28-bit slot indices
     // 1. big spheres
     std::vector<float> radii(n);
-    for (uint32_t i = 0; i < n; i++) radii[i] = sph[i].geometry.w;
+    for (uint32_t i = 0; i < n; i++) radii[i] = std::fabs(sph[i].geometry.w);   // size, whatever the sign
     std::vector<float> sorted = radii;
     std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
     const float median = sorted[n / 2];
@@ -295,7 +297,7 @@ void build_lbvh_host(const Sphere* sph, uint32_t n, HostBvh& out, bool sah, uint
         const float c[3] = {sph[i].geometry.x, sph[i].geometry.y, sph[i].geometry.z};
         for (int k = 0; k < 3; k++) { cmin[k] = std::min(cmin[k], c[k]); cmax[k] = std::max(cmax[k], c[k]); }
         out.small_rmax = std::max(out.small_rmax, radii[i]);
-        out.small_rmin = std::min(out.small_rmin, radii[i]);   // NaN radii keep INFINITY: slack off
+        out.small_rmin = std::min(out.small_rmin, radii[i]);
         prims.push_back(Prim{0, i});
     }
     if (prims.empty()) return;
@@ -305,7 +307,7 @@ void build_lbvh_host(const Sphere* sph, uint32_t n, HostBvh& out, bool sah, uint
         for (int k = 0; k < 3; k++) {
             const float ext = cmax[k] - cmin[k];
             float f = ext > 0.0f ? (c[k] - cmin[k]) / ext : 0.5f;
-            f = std::min(std::max(f, 0.0f), 1.0f);
+            f = !(f > 0.0f) ? 0.0f : std::min(f, 1.0f);   // NaN (an extent that overflows to inf) -> 0, as fmaxf
             q[k] = std::min(1023u, uint32_t(f * 1024.0f));
         }
         p.code = (expand_bits(q[0]) << 2) | (expand_bits(q[1]) << 1) | expand_bits(q[2]);

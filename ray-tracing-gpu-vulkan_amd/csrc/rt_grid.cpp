@@ -18,6 +18,8 @@ bool grid_layout(const float lo[3], const float hi[3], uint32_t m, float rmax, f
                  GridInfo& gi, uint64_t* ref_bound) {
     gi = GridInfo{};
     double ext[3], vol = 1.0;
+    for (int k = 0; k < 3; k++)   // bounds that overflowed to inf (finite spheres near FLT_MAX): no grid
+        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return false;
     for (int k = 0; k < 3; k++) {
         ext[k] = std::max(double(hi[k]) - lo[k], 1e-6);
         vol *= std::max(ext[k], 2.0 * rmax);   // a flat layer counts one sphere diameter thick
@@ -59,9 +61,10 @@ bool build_grid_host(const Sphere* sph, uint32_t n, const std::vector<uint32_t>&
         const rt_vec4& g = sph[i].geometry;
         const float c[3] = {g.x, g.y, g.z};
         if (!std::isfinite(g.x) || !std::isfinite(g.y) || !std::isfinite(g.z) || !std::isfinite(g.w)) return false;
+        const float r = std::fabs(g.w);   // the gate's box is the same for r and -r
         for (int k = 0; k < 3; k++) {
-            lo[k] = std::min(lo[k], c[k] - g.w);
-            hi[k] = std::max(hi[k], c[k] + g.w);
+            lo[k] = std::min(lo[k], c[k] - r);
+            hi[k] = std::max(hi[k], c[k] + r);
         }
         rmin = std::min(rmin, std::fabs(g.w));
         rmax = std::max(rmax, std::fabs(g.w));
@@ -93,9 +96,10 @@ bool build_grid_host(const Sphere* sph, uint32_t n, const std::vector<uint32_t>&
             if (is_big[i]) continue;
             const rt_vec4& g = sph[i].geometry;
             uint32_t a[3], b[3];
-            range(0, g.x, g.w, a[0], b[0]);
-            range(1, g.y, g.w, a[1], b[1]);
-            range(2, g.z, g.w, a[2], b[2]);
+            const float r = std::fabs(g.w);
+            range(0, g.x, r, a[0], b[0]);
+            range(1, g.y, r, a[1], b[1]);
+            range(2, g.z, r, a[2], b[2]);
             for (uint32_t z = a[2]; z <= b[2]; z++)
                 for (uint32_t y = a[1]; y <= b[1]; y++)
                     for (uint32_t x = a[0]; x <= b[0]; x++) {

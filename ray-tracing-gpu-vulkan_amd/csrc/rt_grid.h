@@ -3,6 +3,7 @@
 // (rt_kernels.hip grid_walk). Replaces the driver BVH of src/vulkan.h:395-554 like the LBVH does.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -10,6 +11,17 @@
 #include "rt_internal.h"
 
 namespace rt {
+
+// The geometry contract: index of the first sphere whose centre or radius has a
+// NaN or infinite component, or n when every sphere is finite. The scene calls refuse such a scene
+// before any builder or kernel sees it; finite geometry of any sign or size is rendered.
+inline uint32_t first_nonfinite_geometry(const Sphere* spheres, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) {
+        const rt_vec4& g = spheres[i].geometry;
+        if (!std::isfinite(g.x) || !std::isfinite(g.y) || !std::isfinite(g.z) || !std::isfinite(g.w)) return i;
+    }
+    return n;
+}
 
 struct HostGrid {
     GridInfo info{};

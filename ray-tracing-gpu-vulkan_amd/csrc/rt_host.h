@@ -38,6 +38,9 @@ void keep_row_weights(rt_context* ctx);
 // Message of the calling thread's last failure (rt_last_error()).
 extern thread_local std::string g_last_error;
 int fail(int code, const std::string& msg);
+// RT_ERR_INVALID_ARGUMENT for a scene whose sphere `index` has a NaN / inf centre or radius
+// (the geometry contract; rt_grid.h first_nonfinite_geometry).
+int refuse_nonfinite(uint32_t index);
 int current_device_count(int* n);
 
 // RAII device selection: restores the caller's current device.

@@ -46,6 +46,7 @@
 #include "../../include/rt_abi.h"
 #include "../../include/rt_mi355x.h"
 #include "../../include/rt_mi355x_debug.h"
+#include "rt_grid.h"
 #include "rt_host.h"
 #include "rt_internal.h"
 #include "rt_plan.h"
@@ -577,6 +578,9 @@ int rt_multi_device_count(const rt_multi* m, uint32_t* n) {
 int rt_multi_set_scene(rt_multi* m, const Sphere* spheres, uint32_t count) {
     if (!m) return fail(RT_ERR_INVALID_ARGUMENT, "m is NULL");
     if (!spheres && count) return fail(RT_ERR_INVALID_ARGUMENT, "spheres is NULL");
+    // the geometry contract: refused here, the stored scene and every device's stand
+    if (const uint32_t bad = rt::first_nonfinite_geometry(spheres, count); bad < count)
+        return rt::refuse_nonfinite(bad);
     try {
         m->spheres.assign(spheres, spheres + count);
     } catch (const std::exception& e) {

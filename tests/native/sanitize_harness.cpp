@@ -13,8 +13,14 @@
 //     device times and row weights, malformed inputs;
 //   * the CPU oracle (oracle/rt_oracle.cpp): scenes, small frames in both streams, with a rows map
 //     and accumulation, the tonemap.
+// The geometry contract is driven here too: degenerate finite scenes (negative and
+// zero radii, exact duplicates, concentric shells, a 100:1 radius ratio, radii and centres at
+// 1e-30 / 1e30 and extents that overflow to inf) must build with every sphere's box inside its
+// leaf's and its ancestors' boxes and listed by every grid cell it overlaps; non-finite scenes are
+// only shown to first_nonfinite_geometry, which the scene calls refuse them by.
 // Every structural property is checked; the process exits non-zero on the first violation (and
 // the sanitizers abort on the first error).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -100,7 +106,177 @@ std::vector<std::vector<Sphere>> edge_scenes() {
         for (int i = 0; i < 129; i++) { c.insert(c.end(), {-10.0f + 20.0f * float(i) / 128.0f, 0.0f, 0.0f}); r.push_back(0.05f); }
         out.push_back(spheres_at(c, r));
     }
+    // --- degenerate finite geometry: rendered as the oracle renders it ---
+    auto with_radii = [](std::vector<Sphere> s, auto&& f) {
+        for (size_t i = 0; i < s.size(); i++) s[i].geometry.w = f(i, s[i].geometry.w);
+        return s;
+    };
+    // negative radii among the small spheres (every third) ...
+    out.push_back(with_radii(scene(0.0f, 3), [](size_t i, float r) { return i >= 4 && i % 3 == 0 ? -r : r; }));
+    // ... as the largest sphere (the ground, -1000) ...
+    out.push_back(with_radii(scene(0.0f, 11), [](size_t i, float r) { return i == 0 ? -r : r; }));
+    // ... and everywhere
+    out.push_back(with_radii(scene(0.0f, 3), [](size_t, float r) { return -r; }));
+    // zero radii among real spheres
+    out.push_back(with_radii(scene(0.0f, 11), [](size_t i, float r) { return i >= 4 && i % 5 == 0 ? 0.0f : r; }));
+    {   // exact duplicates: 20 positions x 9 identical records' geometry (more than one leaf each)
+        std::vector<float> c, r;
+        for (int i = 0; i < 20; i++) {
+            const float x = uni(-5, 5), z = uni(-5, 5);
+            for (int k = 0; k < 9; k++) { c.insert(c.end(), {x, 0.3f, z}); r.push_back(0.3f); }
+        }
+        out.push_back(spheres_at(c, r));
+    }
+    {   // concentric shells, both signs
+        std::vector<float> c, r;
+        for (int i = 0; i < 6; i++) {
+            const float x = uni(-4, 4), z = uni(-4, 4);
+            for (float rad : {1.0f, 0.9f, -0.8f, 0.5f, -0.45f}) { c.insert(c.end(), {x, 1.0f, z}); r.push_back(rad); }
+        }
+        out.push_back(spheres_at(c, r));
+    }
+    {   // one sphere 100 x the others, once positive and once negative
+        for (float big : {20.0f, -20.0f}) {
+            std::vector<float> c, r;
+            for (int i = 0; i < 200; i++) { c.insert(c.end(), {uni(-8, 8), 0.2f, uni(-8, 8)}); r.push_back(0.2f); }
+            c.insert(c.end(), {0.0f, 20.0f, 30.0f});
+            r.push_back(big);
+            out.push_back(spheres_at(c, r));
+        }
+    }
     return out;
+}
+
+// Finite extremes: they must build (a refusal is for non-finite input only), with no sanitizer report.
+std::vector<std::vector<Sphere>> extreme_scenes() {
+    std::vector<std::vector<Sphere>> out;
+    auto canon = [](size_t at, float x, float y, float z, float r) {
+        std::vector<Sphere> s = scene(0.0f, 3);
+        s[at].geometry = rt_vec4{x, y, z, r};
+        return s;
+    };
+    out.push_back(canon(7, 1.0f, 0.2f, 1.0f, 1e-30f));    // a radius far below every rounding step
+    out.push_back(canon(7, 1.0f, 0.2f, 1.0f, -1e-30f));
+    out.push_back(canon(7, 0.0f, -1e30f, 0.0f, 1e30f));   // a second "ground", 1e30 in size
+    out.push_back(canon(7, 1e30f, 0.0f, -1e30f, 0.2f));   // a small sphere 1e30 away: the Morton frame spans it
+    {   // every sphere 1e30 in size at +-1e30: no big sphere, finite boxes of 2e30
+        std::vector<float> c, r;
+        for (int i = 0; i < 9; i++) {
+            c.insert(c.end(), {i & 1 ? 1e30f : -1e30f, i & 2 ? 1e30f : -1e30f, i & 4 ? 1e30f : -1e30f});
+            r.push_back(i % 3 == 2 ? -1e30f : 1e30f);
+        }
+        out.push_back(spheres_at(c, r));
+    }
+    {   // finite spheres whose boxes and Morton / SAH extents overflow to +-inf
+        std::vector<float> c, r;
+        for (int i = 0; i < 37; i++) {
+            c.insert(c.end(), {i & 1 ? 3e38f : -3e38f, i & 2 ? 3e38f : -3e38f, i & 4 ? 3e38f : float(i)});
+            r.push_back(1e38f);
+        }
+        out.push_back(spheres_at(c, r));
+    }
+    return out;
+}
+
+// Non-finite geometry is refused by index (rt_grid.h first_nonfinite_geometry) before any builder
+// runs: the builders are never called on these scenes.
+void check_nonfinite_refused() {
+    const std::vector<Sphere> base = scene(0.0f, 11);
+    const uint32_t n = uint32_t(base.size());
+    CHECK(rt::first_nonfinite_geometry(base.data(), n) == n);
+    CHECK(rt::first_nonfinite_geometry(base.data(), 0) == 0);
+    CHECK(rt::first_nonfinite_geometry(nullptr, 0) == 0);
+    const float nan = std::nanf(""), inf = INFINITY;
+    for (uint32_t at : {0u, n / 2, n - 1}) {
+        for (int kind = 0; kind < 6; kind++) {
+            std::vector<Sphere> s = base;
+            rt_vec4& g = s[at].geometry;
+            switch (kind) {
+                case 0: g.w = nan; break;    // NaN radius
+                case 1: g.y = nan; break;    // NaN centre
+                case 2: g.w = inf; break;    // +inf radius
+                case 3: g.x = -inf; break;   // -inf centre
+                case 4: g.w = -inf; break;
+                default: g.z = inf; break;
+            }
+            CHECK(rt::first_nonfinite_geometry(s.data(), n) == at);
+            CHECK(rt::first_nonfinite_geometry(s.data(), at) == at);   // a prefix without it is clean
+            s[n - 1].geometry.x = nan;                                // a later one does not hide the first
+            CHECK(rt::first_nonfinite_geometry(s.data(), n) == at);
+        }
+    }
+    // finite extremes and negative / zero radii are not refused
+    for (const auto& s : extreme_scenes()) CHECK(rt::first_nonfinite_geometry(s.data(), uint32_t(s.size())) == s.size());
+    std::vector<Sphere> s = base;
+    s[3].geometry.w = -1.0f;
+    s[4].geometry.w = 0.0f;
+    s[5].geometry.w = -0.0f;
+    s[6].geometry.x = 1e-45f;   // a denormal
+    CHECK(rt::first_nonfinite_geometry(s.data(), n) == n);
+}
+
+// The box the kernels' AABB gate tests for a sphere: centre -/+ |radius|.
+void sphere_box(const Sphere& s, float lo[3], float hi[3]) {
+    const float c[3] = {s.geometry.x, s.geometry.y, s.geometry.z}, r = std::fabs(s.geometry.w);
+    for (int k = 0; k < 3; k++) { lo[k] = c[k] - r; hi[k] = c[k] + r; }
+}
+
+// Every sphere of a leaf lies inside the leaf's box and every ancestor's, up to the root.
+void check_tree_contains(const std::vector<Sphere>& s, const rt::HostBvh& b) {
+    std::vector<uint32_t> chain;   // the inner nodes whose subtree holds node j
+    for (uint32_t j = 0; j < b.nodes.size(); j++) {
+        while (!chain.empty() && b.nodes[chain.back()].escape <= j) chain.pop_back();   // (the last escapes are ~0u)
+        const rt::BvhNode& nd = b.nodes[j];
+        if (nd.first_count == 0u) {
+            chain.push_back(j);
+            continue;
+        }
+        const uint32_t first = nd.first_count >> 4, count = nd.first_count & 15u;
+        CHECK(count >= 1 && count <= 4 && size_t(first) + count <= b.leaf_ids.size());
+        chain.push_back(j);
+        for (uint32_t k = first; k < first + count; k++) {
+            const uint32_t id = b.leaf_ids[k];
+            CHECK(id < s.size());
+            float lo[3], hi[3];
+            sphere_box(s[id], lo, hi);
+            for (uint32_t a : chain) {
+                const rt::BvhNode& an = b.nodes[a];
+                CHECK(lo[0] >= an.lox && lo[1] >= an.loy && lo[2] >= an.loz);
+                CHECK(hi[0] <= an.hix && hi[1] <= an.hiy && hi[2] <= an.hiz);
+            }
+        }
+        chain.pop_back();
+    }
+}
+
+// Every cell a small sphere's box overlaps (no margin) lists the sphere; each cell's ids ascend.
+void check_grid_contains(const std::vector<Sphere>& s, const rt::HostBvh& b, const rt::HostGrid& grid) {
+    const rt::GridInfo& gi = grid.info;
+    for (uint32_t c = 0; c < gi.n_cells; c++)
+        for (uint32_t j = grid.cell_start[c] + 1; j < grid.cell_start[c + 1]; j++) CHECK(grid.ids[j - 1] < grid.ids[j]);
+    std::vector<char> is_big(s.size(), 0);
+    for (uint32_t id : b.big_ids) is_big[id] = 1;
+    for (uint32_t i = 0; i < s.size(); i++) {
+        if (is_big[i]) continue;
+        float lo[3], hi[3];
+        sphere_box(s[i], lo, hi);
+        uint32_t a[3], z[3];
+        for (int k = 0; k < 3; k++) {
+            const double x0 = std::floor((double(lo[k]) - gi.gmin[k]) / gi.cs[k]);
+            const double x1 = std::floor((double(hi[k]) - gi.gmin[k]) / gi.cs[k]);
+            CHECK(x0 <= x1);
+            a[k] = uint32_t(std::min<double>(gi.n[k] - 1, std::max(0.0, x0)));
+            z[k] = uint32_t(std::min<double>(gi.n[k] - 1, std::max(0.0, x1)));
+        }
+        for (uint32_t zz = a[2]; zz <= z[2]; zz++)
+            for (uint32_t y = a[1]; y <= z[1]; y++)
+                for (uint32_t x = a[0]; x <= z[0]; x++) {
+                    const uint32_t c = (zz * gi.n[1] + y) * gi.n[0] + x;
+                    const uint32_t* f = grid.ids.data() + grid.cell_start[c];
+                    const uint32_t* l = grid.ids.data() + grid.cell_start[c + 1];
+                    CHECK(std::binary_search(f, l, i));
+                }
+    }
 }
 
 void check_tree(const std::vector<Sphere>& s, bool sah) {
@@ -123,6 +299,7 @@ void check_tree(const std::vector<Sphere>& s, bool sah) {
             seen[id]++;
     }
     for (size_t i = 0; i < s.size(); i++) CHECK(seen[i] >= 1);
+    check_tree_contains(s, b);
     rt::HostGrid grid;
     if (rt::build_grid_host(s.data(), uint32_t(s.size()), b.big_ids, 64.0f * 0x1p-24f * 1100.0f, rt::kGridCellScaleHost,
                             1u << 22, grid)) {
@@ -130,6 +307,7 @@ void check_tree(const std::vector<Sphere>& s, bool sah) {
         for (size_t c = 0; c + 1 < grid.cell_start.size(); c++) CHECK(grid.cell_start[c] <= grid.cell_start[c + 1]);
         CHECK(grid.cell_start.back() == grid.ids.size() && grid.ids.size() == grid.rec.size());
         for (uint32_t id : grid.ids) CHECK(id < s.size());
+        check_grid_contains(s, b, grid);
     }
 }
 
@@ -255,6 +433,11 @@ int main() {
         check_tree(s, true);
         check_tree(s, false);
     }
+    for (const auto& s : extreme_scenes()) {
+        check_tree(s, true);
+        check_tree(s, false);
+    }
+    check_nonfinite_refused();
     {   // config 5: 99 860 spheres, the Morton tree (the device build's host twin) and the grid layout
         const std::vector<Sphere> s = scene(0.0f, 158);
         CHECK(s.size() == 99860);
