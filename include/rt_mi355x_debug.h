@@ -37,7 +37,8 @@ int rt_debug_kernel_times(rt_context* ctx, float* out_ms, uint32_t capacity, uin
  * shading records in LDS), "grid_full_slack", "units_per_lane", "unit_min_samples",
  * "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule" (0 LPT, 1 row-major, 2 LPT by tile
  * sum), "refill_reserve", "isolate_tiles", "sah_knobs". Unknown keys: RT_ERR_INVALID_ARGUMENT.
- * Scene-build keys (grid, grid_scale, sah_knobs) apply from the next rt_set_scene. The library
+ * Scene-build keys (grid, grid_scale, sah_knobs) apply from the next rt_set_scene. Values other
+ * than -1 must be finite and within [0, 2^32]: RT_ERR_INVALID_ARGUMENT otherwise. The library
  * reads no environment variable for any of them. */
 int rt_debug_tune(rt_context* ctx, const char* key, double value);
 /* Diagnostic: of ctx's last launch, {sample chunks per pixel (low 16 bits: of the LPT order's tail
@@ -46,6 +47,28 @@ int rt_debug_tune(rt_context* ctx, const char* key, double value);
  * grid walk was the one-layer form, the grid one cell thick in y; bit 17: its camera rays started
  * at the camera position itself, the pinhole shortcut), its dynamic LDS bytes, CU count}. */
 int rt_debug_launch_info(rt_context* ctx, uint32_t* out4);
+/* The single-device launch plan (csrc/rt_launch.h): every host decision that shapes a trace launch,
+ * as a function of plain inputs. `inputs` is an rt::launch::Inputs and `plan` an rt::launch::Plan,
+ * both flat structs of 4-byte words followed by doubles whose first two words are the layout
+ * version (1) and the struct's size (rtvk/abi.py LaunchInputs / LaunchPlan mirror them); in_bytes /
+ * plan_bytes must equal those sizes.
+ * ctx NULL: computes *plan from *inputs. Host only, no device needed: the kernels' answers (block
+ * sizes, the one-layer grid form, occupancies) come from the tables inside *inputs. The inputs must
+ * lie in the domain rt_render_device and rt_debug_tune admit (band 1 .. 65535 each way, known accel
+ * and rng_mode, tuning values -1 or within [0, 2^32]); a band of 2^26 tiles is refused with "band
+ * too large", an occupancy the table does not answer with RT_ERR_DEVICE.
+ * ctx given: copies out the inputs and the plan of ctx's last launch, the inputs with the
+ * occupancies that launch queried, so the ctx-NULL call on them gives the same plan. (After an
+ * adaptive frame: its last pass, whose tile list is not part of the inputs.) RT_ERR_INVALID_ARGUMENT
+ * before the first launch of a scene. */
+int rt_debug_launch_plan(rt_context* ctx, void* inputs, uint64_t in_bytes, void* plan, uint64_t plan_bytes);
+/* The per-row weights rt_launch_row_weights derives from a launch's tile-cost record (csrc/rt_launch.h
+ * row_weights), on hand-made arrays. Host only. cost: n tile records, row-major, tiles_x per tile
+ * row; order: the n tiles in the order they were handed out, or NULL; head_tiles / head_chunks /
+ * chunks: the launch's split of that order; weights: band_h doubles. A tile the order does not
+ * name (an entry >= n is skipped) counts as rank 0; tiles_x 0 gives zeros. */
+int rt_debug_row_weights(const uint32_t* cost, const uint32_t* order, uint32_t n, uint32_t tiles_x, uint32_t band_h,
+                         uint32_t head_tiles, uint32_t head_chunks, uint32_t chunks, double* weights);
 /* Diagnostic: per-phase cycle sums of ctx's last launch, filled only by -DRT_STAMPS builds. */
 int rt_debug_stamps(rt_context* ctx, uint64_t* out8);
 /* Diagnostic: lane utilisation of ctx's last launch per kernel code point k (0..15), filled only by

@@ -27,6 +27,7 @@
 #include "rt_grid.h"
 #include "rt_host.h"
 #include "rt_internal.h"
+#include "rt_launch.h"
 
 namespace rt {
 hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
@@ -53,29 +54,7 @@ hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b,
                                    uint32_t* sample_count, hipStream_t st);
 }  // namespace rt
 
-// Launch-plan parameters that tests and A/B scripts vary through rt_debug_tune() (per context; the
-// shipped defaults are the measured best). None changes an image. The library reads
-// no environment variable for them: only RT_RNG (ray_trace) and RT_BVH_BUILD are read, both
-// documented.
-struct Tuning {
-    static constexpr double kUnset = -1.0;
-    double grid = kUnset;               // 0: no uniform grid (LBVH walks only)
-    double grid_scale = kUnset;         // cell size scale (rt_grid.h kGridCellScale)
-    double grid_coop = kUnset;          // 1: the wave-cooperative grid walk
-    double grid_cq = kUnset;            // 1: the wave-wide candidate queue in the LDS grid walk (§4.9)
-    double grid_rec = kUnset;           // 0: no shading records in the LDS grid kernel's LDS
-    double grid_full_slack = kUnset;    // 1: the full cull slack in grid walks
-    double units_per_lane = kUnset;     // sample-chunk targets (counter-based stream)
-    double unit_min_samples = kUnset;
-    double sample_chunks = kUnset;      // forced chunk count (tail count when the LPT order is split)
-    double head_chunks = kUnset;        // head / tail split of the LPT order
-    double tail_tiles_pm = kUnset;
-    double schedule = kUnset;           // 0 LPT (longest unit chain), 1 row-major
-    double refill_reserve = kUnset;     // units handed out one by one at the end of the queue
-    double isolate_tiles = kUnset;      // reference stream: waves on the first LPT blocks take no more
-    double sah_knobs = kUnset;          // host SAH builder variants (rt_bvh.h)
-    static double get(double v, double def) { return v == kUnset ? def : v; }
-};
+using rt::launch::Tuning;
 
 // One arena of device-built scenes (rt_context::slot; rt_api.cpp device_build_begin).
 struct SceneSlot {
@@ -129,10 +108,7 @@ struct rt_context {
     // occupancy cache per kernel form, count flag and rng mode, valid for occ_lds bytes
     int occ[rt::ACCEL_COUNT][3][2] = {};   // [form][plain, count_tests, one-layer grid walk][mode]
     size_t occ_lds[rt::ACCEL_COUNT][3][2] = {};
-    size_t lds1_bytes = 0;                       // one node copy + leaves + big table (0: no fit)
-    size_t oct_bytes = 0;                        // 8 octant node copies + leaves + big table (0: no fit)
-    size_t grid_bytes = 0;                       // grid references + offsets + big table (0: no grid / no fit)
-    bool has_grid = false;                       // the scene has a grid (staged in LDS when grid_bytes)
+    bool has_grid = false;                       // the scene has a grid
     float grid_pad_radius = 0.0f;                // camera radius the grid's margin covers
     // unpadded LBVH node boxes (host) and the radius the device copy is padded for
     std::vector<rt::BvhNode> nodes_host;
@@ -160,11 +136,10 @@ struct rt_context {
     // kernel clears what it reads)
     unsigned long long* fixed = nullptr;
     uint64_t fixed_cap = 0;                      // texels
-    uint32_t last_chunks = 1;
-    uint32_t last_accel = 0;                     // kernel form (rt::ACCEL_*) of the last launch, 0 = none yet
-    size_t last_lds = 0;                         // its dynamic LDS bytes
-    bool last_flat = false;                      // its grid walk was the one-layer form
-    bool last_pinhole = false;                   // its camera rays started at lf (TraceParams::pinhole_lf)
+    // the last launch's plan (rt_launch.h; accel 0 = none yet) and what it was computed from, with
+    // the occupancies it queried (rt_debug_launch_info, rt_debug_launch_plan)
+    rt::launch::Plan last_plan;
+    rt::launch::Inputs last_in;
     // every colour the shaders can return lies in [0, 1] (RT_RNG_SAMPLE_HASH's fixed point needs it)
     bool colours_unit = true;
     // HIP events bracketing the trace kernel of the last kKernelEvents launches (ring; timing
@@ -257,29 +232,6 @@ void make_octant_orders(const std::vector<rt::BvhNode>& n, std::vector<rt::BvhNo
     }
 }
 
-// LDS budget of the staged forms: 160 KiB per CU, one 1024-thread block per CU; 4 KiB kept free.
-constexpr size_t kMaxLdsBytes = 156 * 1024;
-// ... and of a form that must keep two 768-thread blocks per CU (static + dynamic LDS).
-constexpr size_t kTwoBlockLdsBytes = 78 * 1024;
-// The LDS walk's leaf words hold a leaf index in 10 bits (<= 4096 slots of 4) and an escape node
-// of the 8 copies in 19 bits.
-constexpr uint32_t kMaxLdsLeafSlots = 4096;
-constexpr uint32_t kMaxLdsNodes = 0x7fffeu / 8u;
-
-void size_lds_forms(rt_context* ctx) {
-    const rt::DeviceScene& d = ctx->scene;
-    const size_t tree = size_t(2 * d.n_nodes + d.n_leaf + (d.n_leaf + 3) / 4) * 16;
-    const size_t lds1 = tree;   // shading records stay in HBM (rt_kernels.hip)
-    const bool ok = d.n_nodes && d.n_leaf <= kMaxLdsLeafSlots && d.n_nodes <= kMaxLdsNodes;
-    ctx->lds1_bytes = (ok && lds1 <= kMaxLdsBytes) ? lds1 : 0;
-    const size_t oct = lds1 + size_t(14u) * d.n_nodes * 16u;
-    ctx->oct_bytes = (ok && oct <= kMaxLdsBytes) ? oct : 0;
-    const rt::GridInfo& g = d.grid;
-    const size_t grid = (size_t(g.n_refs) + (g.n_refs + 3) / 4 + (size_t(g.n_cells) + 4) / 4) * 16;
-    ctx->grid_bytes = (g.n_refs && grid + rt::kLaneSumLdsBytes <= kMaxLdsBytes) ? grid : 0;
-}
-
-
 // Stream chaining of a context's device operations (rt_context::ev_last).
 int order_on(rt_context* ctx, hipStream_t st) {
     if (ctx->ev_valid && ctx->last_stream != st) RT_HIP(hipStreamWaitEvent(st, ctx->ev_last, 0));
@@ -315,6 +267,25 @@ int sync_issued(rt_context* ctx) {
     if (ctx->ev_valid) RT_HIP(hipEventSynchronize(ctx->ev_last));
     if (ctx->prev_valid) RT_HIP(hipEventSynchronize(ctx->ev_prev));
     return RT_OK;
+}
+
+// The counters of the last launch, after a host wait for it (rt_get_stats and the rt_debug_* readers).
+int read_counters(rt_context* ctx, rt::Counters* c) {
+    rt::DeviceGuard g(ctx->device);
+    if (int rc = sync_issued(ctx)) return rc;
+    RT_HIP(hipMemcpy(c, ctx->counters, sizeof(*c), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// The end of a render call on `st`: the next build into the current scene's arena waits for its
+// launches, and the call becomes the context's last operation.
+int render_issued(rt_context* ctx, hipStream_t st) {
+    if (ctx->slot_cur >= 0) {
+        SceneSlot& sl = ctx->slot[ctx->slot_cur];
+        RT_HIP(hipEventRecord(sl.ev_free, st));
+        sl.used = true;
+    }
+    return mark_issued(ctx, st);
 }
 
 // One device blob for a host-built scene (rt_context::blob): add() the arrays, then commit()
@@ -705,7 +676,6 @@ int commit_host_package(rt_context* ctx, const rt::HostPackage& pk, hipStream_t 
         up.add(pk.grid.ids, &d.grid_ids);
         ctx->grid_pad_radius = pk.pad_radius;
     }
-    size_lds_forms(ctx);
     up.add(pk.bvh.nodes, &d.nodes);
     up.add(pk.bvh.leaf_geom, &d.leaf_geom);
     up.add(pk.bvh.leaf_ids, &d.leaf_ids);
@@ -911,7 +881,6 @@ int device_build_end(rt_context* ctx) {
     ctx->gpu_tree = true;
     ctx->treelet_stale = true;
     ctx->nodes_host.clear();
-    size_lds_forms(ctx);
     return RT_OK;
 }
 
@@ -946,7 +915,7 @@ int check_scene_args(rt_context* ctx, const Sphere* spheres, uint32_t count, boo
 // reports its default form until it renders.
 int scene_done(rt_context* ctx, int rc) {
     ctx->scene_set = rc == RT_OK;
-    ctx->last_accel = 0;
+    ctx->last_plan.accel = 0;
     return rc;
 }
 
@@ -1020,75 +989,87 @@ int scene_call(rt_context* ctx, const Sphere* spheres, uint32_t count, bool devi
     return scene_done(ctx, rc);
 }
 
-// Kernel form of a launch (rt_internal.h ACCEL_*) and its dynamic LDS bytes. form =
-// options.reserved[1] (A/B and tests, 0 = automatic): 6 one LDS node copy, 8 octant copies, 10
-// every node from L2, 12 the grid, 14 the grid with the wave-cooperative walk; cam_r = the camera's
-// distance from the origin (the grid's margin covers cameras within its pad radius).
-uint32_t choose_accel(const rt_context* ctx, bool brute, uint32_t form, float cam_r, size_t* lds_out) {
-    const rt::DeviceScene& d = ctx->scene;
-    const Tuning& tu = ctx->tune;
-    uint32_t accel;
-    size_t lds = 0;
-    if (brute) {
-        accel = rt::ACCEL_BRUTE;
-    } else if (ctx->has_grid && cam_r <= ctx->grid_pad_radius &&
-               (form == 12u || form == 14u || form == 16u || (form == 0u && (ctx->grid_bytes || !ctx->oct_bytes)))) {
-        // the grid: staged in LDS when it fits (config 3: 1 % faster than the
-        // octant tree), else the octant tree when that fits LDS (a device-built scene of ~1000
-        // spheres, whose grid would be read from L2), else the grid from L2
-        accel = ctx->grid_bytes ? rt::ACCEL_GRID : rt::ACCEL_GRID_GLOBAL;
-        lds = ctx->grid_bytes;   // 0: the grid from L2
-        // the wave-cooperative walk: form 14, or tuning grid_coop = 1
-        const bool coop = form == 14u || (form == 0u && Tuning::get(tu.grid_coop, 0) == 1);
-        if (coop && accel == rt::ACCEL_GRID &&
-            ctx->grid_bytes + rt::kLaneSumLdsBytes + rt::kCoopLdsBytes <= kMaxLdsBytes)
-            accel = rt::ACCEL_GRID_COOP;
-        else if (coop && accel == rt::ACCEL_GRID_GLOBAL)
-            accel = rt::ACCEL_GRID_GLOBAL_COOP;
-        // the LDS grid kernel also stages the winner's gate and shading records ({c, r} + the
-        // material record, 48 B per sphere) when two blocks per CU still fit;
-        // tuning grid_rec = 0: not (A/B)
-        // (the kernel's static table of kRecStatic records: scenes of at most that many spheres)
-        const size_t rec_bytes = d.n_spheres <= rt::kRecStatic ? size_t(rt::kRecStatic) * 48u : kMaxLdsBytes;
-        // the wave-wide candidate queue: form 16, or tuning grid_cq = 1
-        const bool cq = accel == rt::ACCEL_GRID && (form == 16u || (form == 0u && Tuning::get(tu.grid_cq, 0) == 1));
-        const size_t cq_bytes = cq ? rt::kCqLdsBytes : 0u;
-        if (accel == rt::ACCEL_GRID && Tuning::get(tu.grid_rec, 1) != 0 &&
-            ctx->grid_bytes + rec_bytes + rt::kLaneSumLdsBytes + cq_bytes <= kTwoBlockLdsBytes) {
-            accel = cq ? rt::ACCEL_GRID_REC_CQ : rt::ACCEL_GRID_REC;
-            lds = ctx->grid_bytes;   // (the records: static LDS of the kernel)
-        } else if (cq && ctx->grid_bytes + rt::kLaneSumLdsBytes + cq_bytes <= kMaxLdsBytes) {
-            accel = rt::ACCEL_GRID_CQ;
-        }
-    } else if (ctx->oct_bytes && (form == 0u || form == 8u)) {
-        accel = rt::ACCEL_LBVH_OCT;
-        lds = ctx->oct_bytes;
-    } else if (ctx->lds1_bytes && (form == 0u || form == 6u || form == 8u)) {
-        accel = rt::ACCEL_LBVH_LDS;
-        lds = ctx->lds1_bytes;
-    } else if (ctx->gpu_tree && d.treelet && d.n_nodes && d.n_leaf < (1u << 26) && form != 10u) {
-        // (treelet leaf words carry first_count in 30 bits)
-        accel = rt::ACCEL_LBVH_TOP;
-        lds = size_t(rt::kTreeletCap) * 32u;
-    } else {
-        accel = rt::ACCEL_LBVH_GLOBAL;
-    }
-    *lds_out = lds;
-    return accel;
-}
-
 // The launch parameters rt_render_device and rt_render_adaptive_device share: everything that
 // does not depend on how the band's samples are split into units.
 struct TraceSetup {
     rt::TraceParams P;
-    uint32_t accel = 0;          // kernel form (rt::ACCEL_*)
-    bool count = false;          // instrumented build (options.reserved[0] bit 0)
-    bool flat = false;           // one-layer grid walk
-    int mode = 0, ci = 0;        // rt::MODE_*, index of the occupancy cache
-    size_t lds = 0;              // dynamic LDS bytes
-    uint64_t blk = 0, lanes = 0; // block size, lanes of a full grid
+    rt::launch::Inputs in;       // what the plan is computed from
+    rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
     uint64_t tiles_x = 0, n_tiles = 0;
 };
+
+// The kernels' translation unit as the plan sees it (rt_launch.h Device; user = a PlanDevice). The
+// launch's own occupancy query goes through the per-context cache; every answer is noted in the
+// inputs, which rt_debug_launch_plan exports.
+struct PlanDevice {
+    rt_context* ctx;
+    rt::launch::Inputs* in;
+    rt::launch::Device device() {
+        return rt::launch::Device{this, device_occupancy, device_flat_grid_form, device_block_size};
+    }
+    static int device_occupancy(void* user, uint32_t accel, bool count, int mode, bool flat, size_t lds, bool probe);
+    static bool device_flat_grid_form(void* user, const rt::launch::Inputs& in, uint32_t accel, bool count);
+    static uint32_t device_block_size(void*, uint32_t accel) { return rt::block_size(accel); }
+};
+int PlanDevice::device_occupancy(void* user, uint32_t accel, bool count, int mode, bool flat, size_t lds, bool probe) {
+    rt_context* ctx = static_cast<PlanDevice*>(user)->ctx;
+    rt::launch::Inputs& in = *static_cast<PlanDevice*>(user)->in;
+    int b = 0;
+    const int ci = count ? 1 : flat ? 2 : 0;
+    if (probe || ctx->occ_lds[accel][ci][mode] != lds) {
+        if (rt::trace_occupancy(accel, count, mode, flat, lds, &b) != hipSuccess) return -1;
+        if (!probe) {
+            ctx->occ[accel][ci][mode] = std::max(1, b);
+            ctx->occ_lds[accel][ci][mode] = lds;
+        }
+    }
+    if (!probe) b = ctx->occ[accel][ci][mode];
+    if (in.n_occ < rt::launch::kOccRows)   // the answer, for rt_debug_launch_plan
+        in.occ[in.n_occ++] = rt::launch::OccRow{accel, (count ? 1u : 0u) | (uint32_t(mode) << 1) | (flat ? 4u : 0u),
+                                                uint32_t(lds), uint32_t(lds), uint32_t(std::max(0, b))};
+    return b;
+}
+bool PlanDevice::device_flat_grid_form(void* user, const rt::launch::Inputs& in, uint32_t accel, bool count) {
+    const rt_context* ctx = static_cast<PlanDevice*>(user)->ctx;
+    rt::TraceParams P;   // the fields flat_grid_form reads
+    std::memset(&P, 0, sizeof(P));
+    P.n_big = in.n_big;
+    P.pinhole_lf = in.pinhole_lf;
+    if (rt::launch::grid_walk(accel)) {
+        P.grid = ctx->scene.grid;
+        P.cell_start = ctx->scene.cell_start;
+    }
+    const bool flat = rt::flat_grid_form(P, accel, count);
+    static_cast<PlanDevice*>(user)->in->flat_grid = flat ? 1u : 0u;
+    return flat;
+}
+
+// The scene, device and tuning part of a plan's inputs.
+void scene_inputs(const rt_context* ctx, rt::launch::Inputs& in) {
+    const rt::DeviceScene& d = ctx->scene;
+    in = rt::launch::Inputs{};
+    in.bytes = uint32_t(sizeof(in));
+    in.n_spheres = d.n_spheres;
+    in.n_big = d.n_big;
+    in.n_nodes = d.n_nodes;
+    in.n_leaf = d.n_leaf;
+    in.has_grid = ctx->has_grid;
+    in.gpu_tree = ctx->gpu_tree;
+    in.has_treelet = d.treelet != nullptr;
+    for (int k = 0; k < 3; k++) {
+        in.grid_n[k] = d.grid.n[k];
+        in.grid_cs[k] = d.grid.cs[k];
+    }
+    in.grid_n_cells = d.grid.n_cells;
+    in.grid_n_refs = d.grid.n_refs;
+    in.cu_count = uint32_t(ctx->cu_count);
+    in.block_brute = rt::block_size(rt::ACCEL_BRUTE);
+    in.block_walk = rt::block_size(rt::ACCEL_LBVH_GLOBAL);
+    in.small_rmin = d.small_rmin;
+    in.small_rmax = d.small_rmax;
+    in.grid_pad_radius = ctx->grid_pad_radius;
+    in.tune = ctx->tune;
+}
 
 // Argument checks of a render call `who`, before any device work; o = *opt or zeros. *empty: a
 // band without texels, nothing to render.
@@ -1125,7 +1106,6 @@ int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t
         return fail(RT_ERR_INVALID_ARGUMENT,
                     "RT_RNG_SAMPLE_HASH needs every sphere colour channel in [0, 1] (colors[0], and colors[1] of "
                     "checkered spheres); this scene has one outside: render it with RT_RNG_PIXEL_STREAM");
-    (void)mode;
     return RT_OK;
 }
 
@@ -1133,20 +1113,33 @@ int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t
 // occupancy of the kernel form, on the caller's device and stream (after order_on).
 int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
                uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, TraceSetup& S) {
-    const int mode = o.rng_mode == RT_RNG_SAMPLE_HASH ? rt::MODE_HASH : rt::MODE_STREAM;
     const uint32_t spp = rci->samplesPerRenderCall;
     const uint64_t tiles_x = (band_width + 7u) / 8u, tiles_y = (band_height + 7u) / 8u;
     const uint64_t n_tiles = tiles_x * tiles_y;
-    // reserved[1] (internal, A/B only): walk form, 0 = automatic (choose_accel)
     const rt::DeviceScene& d = ctx->scene;
     const float cam_r = std::sqrt(rci->camera_pos.x * rci->camera_pos.x + rci->camera_pos.y * rci->camera_pos.y +
                                   rci->camera_pos.z * rci->camera_pos.z);
-    size_t lds = 0;
-    const uint32_t accel = choose_accel(ctx, o.accel == RT_ACCEL_BRUTE, o.reserved[1], cam_r, &lds);
-    const bool count = (o.reserved[0] & 1u) != 0;  // internal: count box / sphere tests
     rt::TraceParams P;
     std::memset(&P, 0, sizeof(P));
     fill_camera(*rci, P);
+    // the form half of the launch plan (rt_launch.h): kernel form, LDS bytes, cull slack, occupancy
+    rt::launch::Inputs& in = S.in;
+    scene_inputs(ctx, in);
+    in.band_w = band_width;
+    in.band_h = band_height;
+    in.spp = spp;
+    in.rng_mode = o.rng_mode;
+    in.accel = o.accel;
+    in.reserved0 = o.reserved[0];
+    in.reserved1 = o.reserved[1];
+    in.has_rows = rows != nullptr;
+    in.pinhole_lf = P.pinhole_lf;
+    in.cam_r = cam_r;
+    PlanDevice pd{ctx, &in};
+    const char* err = "";
+    if (int rc = rt::launch::plan_form(in, pd.device(), S.plan, &err)) return fail(rc, err);
+    const rt::launch::Plan& plan = S.plan;
+    const uint32_t accel = plan.accel;
     P.number = rci->number;
     P.spp = spp;
     P.max_depth = o.max_depth ? o.max_depth : 50u;
@@ -1172,9 +1165,7 @@ int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
     P.nodes_oct = d.nodes_oct;
     P.treelet = d.treelet;
     P.treelet_count = d.treelet_count;
-    const bool grid_walk = accel == rt::ACCEL_GRID || accel == rt::ACCEL_GRID_GLOBAL || accel == rt::ACCEL_GRID_COOP ||
-                           accel == rt::ACCEL_GRID_GLOBAL_COOP || accel == rt::ACCEL_GRID_REC ||
-                           accel == rt::ACCEL_GRID_CQ || accel == rt::ACCEL_GRID_REC_CQ;
+    const bool grid_walk = rt::launch::grid_walk(accel);
     if (grid_walk) {   // (cell_start also marks a walk)
         P.grid = d.grid;
         P.cell_start = d.cell_start;
@@ -1184,41 +1175,15 @@ int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
     P.n_leaf = d.n_leaf;
     P.leaf_geom = d.leaf_geom;
     P.leaf_ids = d.leaf_ids;
-    // Node-cull slack: a candidate's AABB entry lies at most
-    // 2.75 r + 1.15e-3 t beyond its reported t.
-    P.cull_abs = 3.0f * d.small_rmax + 1e-3f;
-    P.cull_rel = 2e-3f;
-    // Grid walks: the r-term of the slack is there for quadratic false positives
-    // (computed D >= 0, the line passing eps_d <= 7 u |oc|^2 / r outside the sphere, u = 2^-24)
-    // whose AABB entry lies up to ~1.42 r past t. The grid registers a sphere in every cell its AABB
-    // widened by 64 u R + 1e-3 cell overlaps; the 1e-3-cell part is spare (64 u R covers the DDA's
-    // rounding), so while eps_d <= 1e-3 cell the cell holding the ray's closest approach, reached by
-    // best + 1e-3 + 2e-3 best, already references the sphere. eps_d <= 1e-3 cell holds for |oc| <= T
-    // = sqrt(1e-3 cs r_min / 7u) (3/4 of that budget below), and t <= 0.95 T - r_max - 1e-3 cs implies
-    // |oc| <= T. The reported
-    // t lies within 9.1e-4 |oc| (sqrt of D's error, 14 u |oc|^2) of the true or closest-approach t.
-    P.cull_near_t = -1.0f;
-    P.cull_near_abs = P.cull_abs;
-    if (grid_walk && d.small_rmin > 0.0f &&
-        std::isfinite(d.small_rmin)) {
-        const double m = RT_GRID_SPARE * std::min<double>(d.grid.cs[0], std::min<double>(d.grid.cs[1], d.grid.cs[2]));
-        // budget: 3/4 of the spare part for eps_d, 1/4 for a walk that starts (at tmin) up to
-        // 9.1e-4 |oc| ~ 9.1e-4 (r + tmin) past a closest approach just behind tmin
-        const double T = std::sqrt(0.75 * m * double(d.small_rmin) / (7.0 * 0x1p-24));
-        const double tn = 0.95 * T - double(d.small_rmax) - m;
-        const bool start_ok = 9.1e-4 * (double(d.small_rmax) + 1e-3) <= 0.25 * m;
-        if (tn > 0.0 && start_ok && Tuning::get(ctx->tune.grid_full_slack, 0) == 0) {   // grid_full_slack: A/B only
-            P.cull_near_t = float(tn);
-            P.cull_near_abs = 1e-3f + 1e-3f * d.small_rmax;   // covers 9.1e-4 (r + eps_d) of |oc| - t
-        }
-    }
+    P.cull_abs = float(plan.cull_abs);
+    P.cull_rel = float(plan.cull_rel);
+    P.cull_near_t = float(plan.cull_near_t);
+    P.cull_near_abs = float(plan.cull_near_abs);
     P.accum = accum;
     P.out = reinterpret_cast<uint32_t*>(out);
     P.counters = ctx->counters;
 
     {   // a camera outside the padded radius: re-pad the node boxes for it (rare, synchronous)
-        const float cx = rci->camera_pos.x, cy = rci->camera_pos.y, cz = rci->camera_pos.z;
-        const float cam_r = std::sqrt(cx * cx + cy * cy + cz * cz);
         if (!(cam_r <= ctx->pad_radius) && d.n_nodes) {
             if (!std::isfinite(cam_r)) return fail(RT_ERR_INVALID_ARGUMENT, "camera position is not finite");
             ctx->pad_radius = std::max(ctx->scene_radius, cam_r) * 1.01f + 100.0f;
@@ -1240,113 +1205,24 @@ int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
             ctx->padded_for = ctx->pad_radius;
         }
     }
-    // The row map of a banded launch (N > 1 strips) is staged in the walk kernels' dynamic LDS
-    // after their own data (band_row, rt_kernels.hip) when that keeps the blocks per CU; else it
-    // is read from global memory.
-    P.rows_lds = rt::kNoRowsLds;
-    const bool flat = rt::flat_grid_form(P, accel, count);   // the kernel launch_trace picks
-    if (rows && accel != rt::ACCEL_BRUTE) {
-        const size_t off = (lds + 15) & ~size_t(15), with = off + size_t(band_height) * 4u;
-        int b0 = 0, b1 = 0;
-        if (with <= kMaxLdsBytes && rt::trace_occupancy(accel, count, mode, flat, lds, &b0) == hipSuccess &&
-            rt::trace_occupancy(accel, count, mode, flat, with, &b1) == hipSuccess && b1 >= b0 && b1 > 0) {
-            P.rows_lds = uint32_t(off);
-            lds = with;
-        }
-    }
-    // Grid: one persistent block per CU slot the occupancy allows.
-    const int ci = count ? 1 : flat ? 2 : 0;
-    if (ctx->occ_lds[accel][ci][mode] != lds) {
-        int b = 0;
-        RT_HIP(rt::trace_occupancy(accel, count, mode, flat, lds, &b));
-        ctx->occ[accel][ci][mode] = std::max(1, b);
-        ctx->occ_lds[accel][ci][mode] = lds;
-    }
-    const uint64_t blk = rt::block_size(accel);
-    const uint64_t lanes = uint64_t(ctx->cu_count) * ctx->occ[accel][ci][mode] * blk;
+    P.rows_lds = plan.rows_lds;
     S.P = P;
-    S.accel = accel;
-    S.count = count;
-    S.flat = flat;
-    S.mode = mode;
-    S.ci = ci;
-    S.lds = lds;
-    S.blk = blk;
-    S.lanes = lanes;
     S.tiles_x = tiles_x;
     S.n_tiles = n_tiles;
     return RT_OK;
 }
 
-// Sample chunks per pixel (HASH only: the image does not depend on them):
-// enough units for ~128 per lane, but units of at least 256 samples, so the frame is
-// throughput-bound and its tail (the units running when the queue runs dry, about one unit
-// long) short, without paying a unit's start and flush too often (config 3,
-// 10 000 spp, 4 -> 25 chunks -2.0 %; config 5, 1000 spp 4K: 1 / 3 / 7 / 14 chunks 658.6 /
-// 655.3 / 666.0 / 685.9 ms). Tuning sample_chunks forces a count, units_per_lane /
-// unit_min_samples set the targets. The brute-force walk's samples cost ~n/10 times a grid
-// sample, so its floor scales down with n (488 spheres: 5 samples; config 2, 100 spp: 1 -> 20
-// chunks).
-// `pixels` / `n_tiles`: the pixels and 8x8 tiles the launch hands out (the band's, or those of an
-// adaptive pass's tile list).
-uint64_t uniform_chunks(const rt_context* ctx, const TraceSetup& S, uint32_t spp, uint64_t pixels, uint64_t n_tiles,
-                        bool* forced) {
-    const rt::DeviceScene& d = ctx->scene;
-    const int mode = S.mode;
-    const uint32_t accel = S.accel;
-    const uint64_t lanes = S.lanes;
-    uint64_t chunks = 1;
-    *forced = false;
-    if (mode == rt::MODE_HASH && spp > 1) {
-        // units of >= spp / 32 samples, between 32 and 128 (256 until round 5; 128 for every spp
-        // until round 6): a band of the N = 8 frame (135 rows at 10 000 spp) is capped by this
-        // floor, not by the lanes, and its 256-sample tail units left a tail after the queue ran
-        // dry of 4.9 % of the band; config 5's 270-row band at 1 000 spp had 7
-        // chunks of 143 samples under the 128 floor, a 6-7 ms tail of a 68 ms band: 15 chunks
-        // (32-sample floor) -1.1 / -2.0 % on two bands, configs 3 / 4 unchanged (10 000 / 32 >
-        // 128; profiles/r06d_tune2_*.txt)
-        uint64_t per_lane = 128, min_samples = std::min<uint64_t>(128, std::max<uint64_t>(32, spp / 32));
-        if (accel == rt::ACCEL_BRUTE) min_samples = std::min<uint64_t>(256, std::max<uint64_t>(4, 2560 / std::max(1u, d.n_spheres)));
-        per_lane = std::max<uint64_t>(1, uint64_t(Tuning::get(ctx->tune.units_per_lane, double(per_lane))));
-        min_samples = std::max<uint64_t>(1, uint64_t(Tuning::get(ctx->tune.unit_min_samples, double(min_samples))));
-        chunks = std::min<uint64_t>((lanes * per_lane + pixels - 1) / pixels, std::max<uint64_t>(1, spp / min_samples));
-        if (ctx->tune.sample_chunks != Tuning::kUnset) {
-            chunks = uint64_t(ctx->tune.sample_chunks);
-            *forced = true;
-        }
-        chunks = std::max<uint64_t>(1, std::min<uint64_t>({chunks, spp, 4096}));
-        while (chunks > 1 && n_tiles * chunks * 64u >= (1ull << 31)) chunks /= 2;   // unit ids in 32 bits
-    }
-    return chunks;
-}
-
-// Issues one trace launch of S.P (its units, tile order and tables set by the caller): the grid,
-// the block hand-out, the prep kernel and the trace kernel between the launch's two timing events.
+// Issues one trace launch of S.P by S.plan (the units, tile order and tables set by the caller): the
+// prep kernel and the trace kernel between the launch's two timing events.
 int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
     const rt::DeviceScene& d = ctx->scene;
     rt::TraceParams& P = S.P;
-    const uint32_t accel = S.accel;
-    const bool count = S.count;
-    const int mode = S.mode, ci = S.ci;
-    const size_t lds = S.lds;
-    const uint64_t blk = S.blk, n_tiles = S.n_tiles;
-    const uint64_t full = uint64_t(ctx->cu_count) * ctx->occ[accel][ci][mode];
-    const uint64_t by_work = (uint64_t(P.n_units) + blk - 1) / blk;
-    const int grid = int(std::max<uint64_t>(1, std::min(full, by_work)));
-    {   // Block hand-out: the last `reserve` units go out one by one. Measured
-        // (scripts/refill_ab.py, 1080p): 0 to 32 Ki are within 1 %, one pixel per lane of the
-        // grid (262 Ki) is 10-15 % slower at 13-50 spp.
-        const uint64_t reserve = uint64_t(Tuning::get(ctx->tune.refill_reserve, 8192));
-        P.n_block_units = P.n_units > reserve ? uint32_t((P.n_units - reserve) & ~uint64_t(63)) : 0u;
-        P.first_blocks = uint32_t(std::min<uint64_t>(uint64_t(grid) * blk / 64u, P.n_block_units / 64u));
-        // A STREAM frame is as long as its longest pixel chain; the waves that
-        // start on the longest-chain tiles of the LPT order take no further work, so no refill of
-        // their other lanes slows the chain down. 1/512 of the waves (32 on a full MI355X):
-        // 12 spp -3.4 %, 50 spp -3 %, 100 spp +-0 (scripts/env_ab.py isolate_tiles). HASH
-        // units are short: no isolation.
-        const uint64_t iso = uint64_t(Tuning::get(ctx->tune.isolate_tiles, double(uint64_t(grid) * blk / 64u / 512u)));
-        P.isolate_blocks = (P.tile_order && mode == rt::MODE_STREAM) ? uint32_t(std::min<uint64_t>(P.first_blocks, iso)) : 0u;
-    }
+    const rt::launch::Plan& plan = S.plan;
+    const uint32_t accel = plan.accel;
+    const uint64_t n_tiles = S.n_tiles;
+    P.n_block_units = plan.n_block_units;
+    P.first_blocks = plan.first_blocks;
+    P.isolate_blocks = plan.isolate_blocks;
     if (accel == rt::ACCEL_LBVH_TOP && ctx->treelet_stale) {   // after a build, refit or re-pad
         RT_HIP(rt::build_treelet(d.nodes, d.n_nodes, d.treelet, d.treelet_count, st));
         ctx->treelet_stale = false;
@@ -1358,9 +1234,11 @@ int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
     RT_HIP(rt::launch_prep(P, P.first_blocks * 64u, ctx->big_tab, P.tile_cost ? uint32_t(n_tiles) : 0u, st));
     P.big_tab = ctx->big_tab;
     RT_HIP(hipEventRecord(kev[0], st));
-    RT_HIP(rt::launch_trace(P, accel, count, mode, grid, lds, st));
+    RT_HIP(rt::launch_trace(P, accel, plan.count != 0, int(plan.mode), int(plan.grid), plan.lds, st));
     RT_HIP(hipEventRecord(kev[1], st));
     ctx->kev_count++;
+    ctx->last_plan = plan;
+    ctx->last_in = S.in;
     return RT_OK;
 }
 
@@ -1411,7 +1289,7 @@ int adaptive_passes(rt_context* ctx, TraceSetup& S, const rt_options& o, const r
     uint32_t* lists[2] = {a.tiles + n_tiles, a.tiles + 2u * n_tiles};
     // the walk kernels record tile costs unconditionally (rt_kernels.hip record_tile_cost): a
     // scratch table of the whole tile grid, never read
-    P.tile_cost = S.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * n_tiles : nullptr;
+    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * n_tiles : nullptr;
     P.accumulate = 0u;
     P.head_tiles = 0u;
     RT_HIP(rt::launch_adaptive_init(a.state, st));
@@ -1428,13 +1306,12 @@ int adaptive_passes(rt_context* ctx, TraceSetup& S, const rt_options& o, const r
             P.tile_order = list;
             // uniform chunks by rt_render_device's rule for the pixels of the list; no head / tail
             // split (the list carries no cost order)
-            bool forced = false;
-            const uint64_t chunks = uniform_chunks(ctx, S, P.spp, 64u * active, active, &forced);
-            if (active * chunks * 64u >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
-            P.chunks = uint32_t(chunks);
-            P.head_chunks = P.chunks;
-            P.n_units = uint32_t(active * chunks * 64u);
-            ctx->last_chunks = P.chunks;
+            const char* err = "";
+            if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * active, active, list != nullptr, false, &err))
+                return fail(rc, err);
+            P.chunks = S.plan.chunks;
+            P.head_chunks = S.plan.head_chunks;
+            P.n_units = S.plan.n_units;
             if (int rc = launch_units(ctx, S, st)) return rc;
         }
         done += k;
@@ -1513,17 +1390,9 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
     TraceSetup S;
     if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
     rt::TraceParams& P = S.P;
-    const uint32_t accel = S.accel, spp = rci->samplesPerRenderCall;
-    const int mode = S.mode;
-    const uint64_t lanes = S.lanes, tiles_x = S.tiles_x, n_tiles = S.n_tiles;
-    bool chunks_forced = false;
-    uint64_t chunks = uniform_chunks(ctx, S, spp, uint64_t(band_width) * band_height, n_tiles, &chunks_forced);
-    if (n_tiles * chunks * 64u >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
-    P.chunks = uint32_t(chunks);
-    ctx->last_accel = accel;
-    ctx->last_lds = S.lds;
-    ctx->last_flat = S.flat;
-    ctx->last_pinhole = P.pinhole_lf != 0;
+    const uint32_t accel = S.plan.accel, spp = rci->samplesPerRenderCall;
+    const int mode = int(S.plan.mode);
+    const uint64_t tiles_x = S.tiles_x, n_tiles = S.n_tiles;
     const uint64_t texels = uint64_t(band_width) * band_height;
     if (mode == rt::MODE_HASH) {
         if (ctx->fixed_cap < texels) {
@@ -1557,40 +1426,15 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         P.tile_cost = sc.cost[sc.cur];   // zeroed by the launch's prep kernel (-DRT_TILE_COST_SUM
                                          // builds record the tile's summed chains instead of the longest)
     }
-    // Head and tail of the LPT order (HASH): the frame's tail is made of the units
-    // still running when the queue runs dry, so only the last ranks (the shortest fifth of the
-    // tiles) need short units, 2/5 of `chunks` (the count that keeps a uniform split
-    // throughput-bound); the head ranks run longer ones, about 12 per lane (a head unit ~1/12 of
-    // the frame, so it ends while the tail runs), and only when that is fewer chunks than the
-    // tail's (not at 1080p / 1000 spp, whose uniform units are already that long). Config 3:
-    // 25 -> 3 head / 10 tail chunks, config 5: 3 -> 1 / 3. A sixth of the units at config 3, so
-    // fewer unit starts and flushes, and fewer 64-bit fixed-point atomics, whose memory-side requests are most of the
-    // kernel's HBM traffic: 6.6 -> 0.98 GB per frame at -0.6 % frame time (10 tail chunks; 25:
-    // 1.6 GB at -0.9 %; profiles/r03_tail_chunks_traffic.txt). Tuning head_chunks / tail_tiles_pm
-    // (tail tiles per mille) override; sample_chunks sets the tail count itself.
-    uint64_t head_tiles = 0, head_chunks = chunks;
-    if (mode == rt::MODE_HASH && chunks > 1 && P.tile_order) {
-        const uint64_t pixels = uint64_t(band_width) * band_height;
-        head_chunks = std::max<uint64_t>(1, (12u * lanes + pixels - 1) / std::max<uint64_t>(1, pixels));
-        // tail units: at most 2.5x the uniform ones, and at least 3x shorter than the head's
-        const uint64_t tail_chunks =
-            chunks_forced ? chunks : std::max<uint64_t>((chunks * 2 + 4) / 5, std::min<uint64_t>(chunks, 3 * head_chunks));
-        head_chunks = uint64_t(Tuning::get(ctx->tune.head_chunks, double(head_chunks)));
-        // the last 30 % of the tiles (20 % until round 5: the frame's tail after the queue ran
-        // dry 25.5 -> 16.4 ms at config 3, -0.7 %; the N = 8 band with 128-sample units -1.8 %)
-        const uint64_t tail_pm = uint64_t(Tuning::get(ctx->tune.tail_tiles_pm, 300));
-        head_chunks = std::max<uint64_t>(1, std::min<uint64_t>(head_chunks, tail_chunks));
-        const uint64_t tail = std::min<uint64_t>(n_tiles, (n_tiles * std::min<uint64_t>(tail_pm, 1000) + 999) / 1000);
-        if (head_chunks < tail_chunks) {
-            head_tiles = n_tiles - tail;
-            P.chunks = uint32_t(tail_chunks);
-        }
-    }
-    chunks = P.chunks;
-    P.head_tiles = uint32_t(head_tiles);
-    P.head_chunks = uint32_t(head_tiles ? head_chunks : chunks);
-    P.n_units = uint32_t((head_tiles * P.head_chunks + (n_tiles - head_tiles) * chunks) * 64u);
-    ctx->last_chunks = P.chunks | (head_tiles ? P.head_chunks << 16 : 0u);
+    // the unit half of the plan: sample chunks, head / tail split of the LPT order, hand-out
+    S.in.lpt_valid = P.tile_order != nullptr;
+    const char* err = "";
+    if (int rc = rt::launch::split_units(S.in, S.plan, spp, texels, n_tiles, P.tile_order != nullptr, true, &err))
+        return fail(rc, err);
+    P.chunks = S.plan.chunks;
+    P.head_tiles = S.plan.head_tiles;
+    P.head_chunks = S.plan.head_chunks;
+    P.n_units = S.plan.n_units;
     if (P.tile_cost) {   // this launch's chunk split, for the cost normalisation of the next order
         rt::TileSchedule& sc = ctx->sched;
         sc.rec_head_tiles[sc.cur] = P.head_tiles;
@@ -1631,12 +1475,7 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         ctx->sched.cur ^= 1;
         ctx->sched.valid = true;
     }
-    if (ctx->slot_cur >= 0) {   // the next build into this arena waits for this launch
-        SceneSlot& sl = ctx->slot[ctx->slot_cur];
-        RT_HIP(hipEventRecord(sl.ev_free, st));
-        sl.used = true;
-    }
-    return mark_issued(ctx, st);
+    return render_issued(ctx, st);
 }
 
 int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
@@ -1672,22 +1511,13 @@ int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const 
     TraceSetup S;
     if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
     if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, S.n_tiles, st)) return rc;
-    ctx->last_accel = S.accel;
-    ctx->last_lds = S.lds;
-    ctx->last_flat = S.flat;
-    ctx->last_pinhole = S.P.pinhole_lf != 0;
     int rc = adaptive_passes(ctx, S, o, *ad, max_spp, accum, out, sample_count, info, st);
     if (rc != RT_OK) {   // the half-buffers are zero between calls, whatever happened
         const std::string msg = rt::g_last_error;
         (void)hipMemsetAsync(ctx->adaptive.planes, 0, ctx->adaptive.cap * 6u * sizeof(unsigned long long), st);
         rt::g_last_error = msg;
     }
-    if (ctx->slot_cur >= 0) {   // the next build into this arena waits for these launches
-        SceneSlot& sl = ctx->slot[ctx->slot_cur];
-        RT_HIP(hipEventRecord(sl.ev_free, st));
-        sl.used = true;
-    }
-    if (int rc2 = mark_issued(ctx, st)) return rc ? rc : rc2;
+    if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
     return rc;
 }
 
@@ -1703,10 +1533,8 @@ int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, u
 
 int rt_get_stats(rt_context* ctx, rt_stats* out) {
     if (!ctx || !out) return fail(RT_ERR_INVALID_ARGUMENT, "ctx or out is NULL");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     out->segments = c.segments;
     out->samples = c.samples;
     out->box_tests = c.box_tests;
@@ -1752,10 +1580,8 @@ int rt_gather_rows(rt_context* ctx, const float* src_accum, const uint32_t* rows
 // otherwise).
 int rt_debug_util(rt_context* ctx, uint64_t* out32) {
     if (!ctx || !out32) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     for (int k = 0; k < 32; k++) out32[k] = c.util[k];
     return RT_OK;
 }
@@ -1763,10 +1589,8 @@ int rt_debug_util(rt_context* ctx, uint64_t* out32) {
 // Diagnostic export: phase cycle sums of the last launch (RT_STAMPS builds; zeros otherwise).
 int rt_debug_stamps(rt_context* ctx, uint64_t* out8) {
     if (!ctx || !out8) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     for (int k = 0; k < 8; k++) out8[k] = c.stamp[k];
     if (!c.stamp[0] && !c.stamp[1]) out8[6] = c.wave_iters;   // non-stamp builds: walk iterations
     return RT_OK;
@@ -1786,10 +1610,8 @@ int rt_debug_tile_cost(rt_context* ctx, uint32_t* out, uint64_t capacity, uint64
 
 int rt_debug_lane_hist(rt_context* ctx, uint64_t* out68) {
     if (!ctx || !out68) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     std::memcpy(out68, c.lane_hist, sizeof(c.lane_hist));
     out68[65] = c.t_first;
     out68[66] = c.t_dry;
@@ -1799,10 +1621,8 @@ int rt_debug_lane_hist(rt_context* ctx, uint64_t* out68) {
 
 int rt_debug_steals(rt_context* ctx, uint64_t* out) {
     if (!ctx || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     *out = c.steals;
     return RT_OK;
 }
@@ -1811,10 +1631,8 @@ int rt_debug_steals(rt_context* ctx, uint64_t* out) {
 // (rt_internal.h Counters::walk_split).
 int rt_debug_walk_split(rt_context* ctx, uint64_t* out4) {
     if (!ctx || !out4) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     std::memcpy(out4, c.walk_split, sizeof(c.walk_split));
     return RT_OK;
 }
@@ -1823,10 +1641,8 @@ int rt_debug_walk_split(rt_context* ctx, uint64_t* out4) {
 // references} (the decision metric of an occupancy bitmap).
 int rt_debug_grid_cells(rt_context* ctx, uint64_t* out2) {
     if (!ctx || !out2) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     out2[0] = c.box_tests;
     out2[1] = c.cells_empty;
     return RT_OK;
@@ -1835,10 +1651,8 @@ int rt_debug_grid_cells(rt_context* ctx, uint64_t* out2) {
 // Diagnostic export: walk-length histogram of the last COUNT launch (2 x 64 bins: miss, hit).
 int rt_debug_walk_hist(rt_context* ctx, uint64_t* out128) {
     if (!ctx || !out128) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(ctx->device);
-    if (int rc = sync_issued(ctx)) return rc;
     rt::Counters c;
-    RT_HIP(hipMemcpy(&c, ctx->counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (int rc = read_counters(ctx, &c)) return rc;
     std::memcpy(out128, c.walk_hist, sizeof(c.walk_hist));
     return RT_OK;
 }
@@ -1897,26 +1711,8 @@ int launch_row_weights(rt_context* ctx, uint64_t index, std::vector<double>& w) 
         if (sn.launch != index || !sn.pending) continue;
         DeviceGuard g(ctx->device);
         RT_HIP(hipEventSynchronize(sn.ev));
-        // a tile's record is its longest unit chain; x the chunk count of the rank it ran at (the
-        // LPT head / tail split) it estimates its longest pixel's chain, the key the LPT order uses
-        std::vector<uint32_t> rank;
-        if (sn.has_order && sn.head_tiles) {
-            rank.assign(sn.n, 0u);
-            for (uint32_t r = 0; r < sn.n; r++)
-                if (sn.host[sn.n + r] < sn.n) rank[sn.host[sn.n + r]] = r;
-        }
-        const uint32_t tiles_y = sn.tiles_x ? sn.n / sn.tiles_x : 0;
-        std::vector<double> tile_row(tiles_y, 0.0);
-        for (uint32_t t = 0; t < sn.n && sn.tiles_x; t++) {
-            const double mult = rank.empty() ? 1.0 : double(rank[t] < sn.head_tiles ? sn.head_chunks : sn.chunks);
-            if (t / sn.tiles_x < tiles_y) tile_row[t / sn.tiles_x] += double(sn.host[t]) * mult;
-        }
-        w.assign(sn.band_h, 0.0);
-        for (uint32_t i = 0; i < sn.band_h; i++) {
-            const uint32_t ty = i / 8u;
-            const uint32_t rows_in = std::min<uint32_t>(8u, sn.band_h - ty * 8u);
-            if (ty < tiles_y) w[i] = tile_row[ty] / double(rows_in);
-        }
+        rt::launch::row_weights(sn.host, sn.has_order ? sn.host + sn.n : nullptr, sn.n, sn.tiles_x, sn.band_h,
+                                sn.head_tiles, sn.head_chunks, sn.chunks, w);
         return RT_OK;
     }
     return fail(RT_ERR_INVALID_ARGUMENT, "no tile-cost record kept for that launch");
@@ -1953,38 +1749,74 @@ const char* rt_build_info(void) {
 
 int rt_debug_tune(rt_context* ctx, const char* key, double value) {
     if (!ctx || !key) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    static const struct { const char* name; double Tuning::*field; } kKeys[] = {
-        {"grid", &Tuning::grid}, {"grid_scale", &Tuning::grid_scale}, {"grid_coop", &Tuning::grid_coop},
-        {"grid_cq", &Tuning::grid_cq},
-        {"grid_rec", &Tuning::grid_rec}, {"grid_full_slack", &Tuning::grid_full_slack},
-        {"units_per_lane", &Tuning::units_per_lane}, {"unit_min_samples", &Tuning::unit_min_samples},
-        {"sample_chunks", &Tuning::sample_chunks}, {"head_chunks", &Tuning::head_chunks},
-        {"tail_tiles_pm", &Tuning::tail_tiles_pm}, {"schedule", &Tuning::schedule},
-        {"refill_reserve", &Tuning::refill_reserve}, {"isolate_tiles", &Tuning::isolate_tiles},
-        {"sah_knobs", &Tuning::sah_knobs}};
-    if (!(value >= 0.0 || value == Tuning::kUnset))
-        return fail(RT_ERR_INVALID_ARGUMENT, "tuning values are >= 0 (-1 restores the default)");
-    for (const auto& k : kKeys) {
-        if (std::strcmp(k.name, key) == 0) {
-            ctx->tune.*(k.field) = value;
-            return RT_OK;
-        }
-    }
-    return fail(RT_ERR_INVALID_ARGUMENT, std::string("unknown tuning key ") + key);
+    if (!rt::launch::tuning_value_ok(value))
+        return fail(RT_ERR_INVALID_ARGUMENT, "tuning values are finite, >= 0 and <= 2^32 (-1 restores the default)");
+    double Tuning::*field = rt::launch::tuning_field(key);
+    if (!field) return fail(RT_ERR_INVALID_ARGUMENT, std::string("unknown tuning key ") + key);
+    ctx->tune.*field = value;
+    return RT_OK;
 }
 
 int rt_debug_launch_info(rt_context* ctx, uint32_t* out4) {
     if (!ctx || !out4) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    out4[0] = ctx->last_chunks;
-    if (ctx->last_accel) {   // the kernel form the last launch actually ran
-        out4[1] = ctx->last_accel | (ctx->last_flat ? 0x10000u : 0u) | (ctx->last_pinhole ? 0x20000u : 0u);
-        out4[2] = uint32_t(ctx->last_lds);
+    const rt::launch::Plan& p = ctx->last_plan;
+    out4[0] = p.chunks | (p.head_tiles ? p.head_chunks << 16 : 0u);
+    if (p.accel) {   // the kernel form the last launch actually ran
+        out4[1] = p.accel | (p.flat ? 0x10000u : 0u) | (ctx->last_in.pinhole_lf ? 0x20000u : 0u);
+        out4[2] = p.lds;
     } else {   // no launch yet: the default form of the current scene (camera within its pad radius)
+        rt::launch::Inputs in;
+        scene_inputs(ctx, in);
+        rt::launch::Plan q;
+        rt::launch::size_lds_forms(in, q);
         size_t lds = 0;
-        out4[1] = choose_accel(ctx, false, 0u, 0.0f, &lds);
+        out4[1] = rt::launch::choose_accel(in, q, false, 0u, 0.0f, &lds);
         out4[2] = uint32_t(lds);
     }
     out4[3] = uint32_t(ctx->cu_count);
+    return RT_OK;
+}
+
+int rt_debug_launch_plan(rt_context* ctx, void* inputs, uint64_t in_bytes, void* plan, uint64_t plan_bytes) {
+    using rt::launch::Inputs;
+    using rt::launch::Plan;
+    if (!inputs || !plan) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (in_bytes != sizeof(Inputs) || plan_bytes != sizeof(Plan))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_launch_plan: struct size differs from this library's layout (version " +
+                                                 std::to_string(rt::launch::kVersion) + ")");
+    if (ctx) {   // the last launch's
+        if (!ctx->last_plan.accel) return fail(RT_ERR_INVALID_ARGUMENT, "no launch since the last scene call");
+        std::memcpy(inputs, &ctx->last_in, sizeof(Inputs));
+        std::memcpy(plan, &ctx->last_plan, sizeof(Plan));
+        return RT_OK;
+    }
+    Inputs in;
+    std::memcpy(&in, inputs, sizeof(in));
+    if (in.version != rt::launch::kVersion || in.bytes != sizeof(Inputs))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_launch_plan: inputs of another layout version");
+    // the domain rt_render_device and rt_debug_tune admit
+    if (in.band_w == 0 || in.band_h == 0 || in.band_w > 65535u || in.band_h > 65535u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be within 1 .. 65535");
+    if (in.accel > RT_ACCEL_LBVH || in.rng_mode > RT_RNG_SAMPLE_HASH) return fail(RT_ERR_INVALID_ARGUMENT, "unknown accel or rng_mode");
+    if (in.rng_mode == RT_RNG_SAMPLE_HASH && in.spp > rt::kHashMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "RT_RNG_SAMPLE_HASH: samplesPerRenderCall above 2^19");
+    if (in.n_occ > rt::launch::kOccRows) return fail(RT_ERR_INVALID_ARGUMENT, "occupancy table too long");
+    for (uint32_t k = 0; k < rt::launch::kTuningKeys; k++)
+        if (!rt::launch::tuning_value_ok(in.tune.*rt::launch::tuning_field(rt::launch::tuning_key(k))))
+            return fail(RT_ERR_INVALID_ARGUMENT, std::string("tuning value out of range: ") + rt::launch::tuning_key(k));
+    Plan p;
+    const char* err = "";
+    if (int rc = rt::launch::make_plan(in, rt::launch::table_device(in), p, &err)) return fail(rc, err);
+    std::memcpy(plan, &p, sizeof(p));
+    return RT_OK;
+}
+
+int rt_debug_row_weights(const uint32_t* cost, const uint32_t* order, uint32_t n, uint32_t tiles_x, uint32_t band_h,
+                         uint32_t head_tiles, uint32_t head_chunks, uint32_t chunks, double* weights) {
+    if ((!cost && n) || (!weights && band_h)) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::vector<double> w;
+    rt::launch::row_weights(cost, order, n, tiles_x, band_h, head_tiles, head_chunks, chunks, w);
+    std::copy(w.begin(), w.end(), weights);
     return RT_OK;
 }
 

@@ -1,6 +1,6 @@
 // rt_plan.h — the multi-device frame as host data (no HIP): the row partition over the devices
 // and the ordered steps rt_multi executes for one frame. Plain C++ so the CPU tests
-// (rt_debug_multi_plan*, rt_partition_*) and the sanitizer build (oracle/Makefile `sanitize`)
+// (rt_debug_multi_plan*, rt_partition_*) and the sanitizer build (tests/native/Makefile `sanitize`)
 // exercise exactly the code rt_multi runs.
 //
 // Reference: the per-GPU row bands of src/ray_trace.cpp:74-93 (first band takes the remainder)

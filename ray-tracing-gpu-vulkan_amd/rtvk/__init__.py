@@ -26,7 +26,7 @@ __all__ = [
     "DIFFUSE", "METAL", "REFRACTIVE", "SOLID", "CHECKERED", "Sphere", "Scene", "RenderCallInfo",
     "Options", "Stats", "RtError", "generateRandomScene", "canonical_render_call_info",
     "make_options", "Renderer", "MultiRenderer", "render", "ray_trace", "store_ppm", "spheres_to_numpy",
-    "load_library", "HASH", "STREAM", "multi_plan", "partition_strips", "partition_rebalance",
+    "load_library", "HASH", "STREAM", "multi_plan", "launch_inputs", "launch_plan", "row_weights", "struct_dict", "partition_strips", "partition_rebalance",
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
 ]
 
@@ -300,6 +300,14 @@ class Renderer:
                 "form": forms.get(int(v[1]) & 0xffff, str(v[1])), "lds_bytes": int(v[2]), "cus": int(v[3]),
                 "flat_grid": bool((int(v[1]) >> 16) & 1), "pinhole_origin": bool((int(v[1]) >> 17) & 1)}
 
+    def launch_plan(self):
+        """(abi.LaunchInputs, abi.LaunchPlan) of the last launch (rt_debug_launch_plan): the inputs
+        carry the occupancies the launch queried, so rtvk.launch_plan(inputs) recomputes the plan."""
+        inputs, plan = abi.LaunchInputs(), abi.LaunchPlan()
+        check(self._lib.rt_debug_launch_plan(self._ctx, ctypes.byref(inputs), ctypes.sizeof(inputs),
+                                             ctypes.byref(plan), ctypes.sizeof(plan)))
+        return inputs, plan
+
     def scatter_rows(self, src_accum, src_rgba8, rows, dst_accum, dst_rgba8, stream=None) -> None:
         """dst[rows[i]] = src[i] (device), the reorder after a multi-GPU gather; either image may
         be None (both its source and destination)."""
@@ -532,6 +540,66 @@ def partition_rebalance(parts: Sequence, cost: np.ndarray, measured: Optional[Se
                                      m_ms, float(tolerance), ctypes.byref(moved), ctypes.byref(pred)))
     del keep
     return _split(rows, counts), int(moved.value), float(pred.value)
+
+
+def launch_inputs(**kv) -> abi.LaunchInputs:
+    """An abi.LaunchInputs (rt::launch::Inputs, csrc/rt_launch.h) with its header filled and every
+    tuning value unset; fields by keyword (grid_n / grid_cs: sequences of 3; occ: rows of (accel,
+    flags, lds_lo, lds_hi, blocks); tuning values as tune_<key>)."""
+    v = abi.LaunchInputs()
+    v.version, v.bytes = abi.LAUNCH_PLAN_VERSION, ctypes.sizeof(abi.LaunchInputs)
+    for k in abi.TUNING_KEYS:
+        setattr(v, "tune_" + k, -1.0)
+    for k, x in kv.items():
+        if k in ("grid_n", "grid_cs"):
+            for i in range(3):
+                getattr(v, k)[i] = x[i]
+        elif k == "occ":
+            v.n_occ = len(x)
+            for i, row in enumerate(x):
+                v.occ[i] = abi.LaunchOccRow(*row)
+        else:
+            if not hasattr(v, k):
+                raise KeyError(k)
+            setattr(v, k, x)
+    return v
+
+
+def launch_plan(inputs: abi.LaunchInputs) -> abi.LaunchPlan:
+    """The launch plan rt_render_device computes from `inputs` (rt_debug_launch_plan without a
+    context; host only, no GPU needed). Raises RtError for what the library refuses ("band too
+    large", an occupancy the table in the inputs does not answer, values outside the domain)."""
+    plan = abi.LaunchPlan()
+    check(load_library().rt_debug_launch_plan(None, ctypes.byref(inputs), ctypes.sizeof(inputs), ctypes.byref(plan),
+                                              ctypes.sizeof(plan)))
+    return plan
+
+
+def row_weights(cost, order, tiles_x: int, band_h: int, head_tiles: int = 0, head_chunks: int = 1,
+                chunks: int = 1) -> np.ndarray:
+    """Per band row, its share of a launch's work from the tile-cost record `cost` (row-major tiles,
+    tiles_x per tile row) and the hand-out `order` (None: none kept): what rt_launch_row_weights
+    computes for a recorded launch (rt_debug_row_weights; host only)."""
+    c = np.ascontiguousarray(cost, np.uint32)
+    o = None if order is None else np.ascontiguousarray(order, np.uint32)
+    if o is not None and len(o) != len(c):
+        raise ValueError("order and cost must be equally long")
+    w = np.zeros(band_h, np.float64)
+    check(load_library().rt_debug_row_weights(c.ctypes.data if len(c) else None, None if o is None else o.ctypes.data,
+                                              len(c), tiles_x, band_h, head_tiles, head_chunks, chunks,
+                                              w.ctypes.data if band_h else None))
+    return w
+
+
+def struct_dict(s: ctypes.Structure) -> dict:
+    """A ctypes struct of words, doubles and arrays of them as a plain dict (nested lists)."""
+    def val(x):
+        if isinstance(x, ctypes.Array):
+            return [val(e) for e in x]
+        if isinstance(x, ctypes.Structure):
+            return [val(getattr(x, n)) for n, _ in x._fields_]
+        return x
+    return {n: val(getattr(s, n)) for n, _ in s._fields_}
 
 
 PLAN_OPS = {1: "load_rows", 2: "group_start", 3: "send", 4: "recv", 5: "group_end", 6: "render",

@@ -100,6 +100,44 @@ class AdaptiveInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("samples", ctypes.c_uint64)]
 
 
+TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
+               "unit_min_samples", "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule", "refill_reserve",
+               "isolate_tiles", "sah_knobs")
+LAUNCH_PLAN_VERSION = 1
+LAUNCH_OCC_ROWS = 8
+
+
+class LaunchOccRow(ctypes.Structure):
+    """rt::launch::OccRow (csrc/rt_launch.h): accel 0 / flags 0xffffffff match any."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("accel", "flags", "lds_lo", "lds_hi", "blocks")]
+
+
+class LaunchInputs(ctypes.Structure):
+    """rt::launch::Inputs (csrc/rt_launch.h): 4-byte words, then doubles (binary32 values as doubles;
+    the tuning values by name, -1 = unset)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in (
+        "version", "bytes", "n_spheres", "n_big", "n_nodes", "n_leaf", "has_grid", "gpu_tree", "has_treelet")]
+        + [("grid_n", ctypes.c_uint32 * 3)]
+        + [(n, ctypes.c_uint32) for n in (
+            "grid_n_cells", "grid_n_refs", "cu_count", "band_w", "band_h", "spp", "rng_mode", "accel", "reserved0",
+            "reserved1", "has_rows", "lpt_valid", "pinhole_lf", "block_brute", "block_walk", "flat_grid", "n_occ")]
+        + [("occ", LaunchOccRow * LAUNCH_OCC_ROWS), ("pad_", ctypes.c_uint32)]
+        + [("small_rmin", ctypes.c_double), ("small_rmax", ctypes.c_double), ("grid_cs", ctypes.c_double * 3),
+           ("grid_pad_radius", ctypes.c_double), ("cam_r", ctypes.c_double)]
+        + [("tune_" + k, ctypes.c_double) for k in TUNING_KEYS])
+
+
+class LaunchPlan(ctypes.Structure):
+    """rt::launch::Plan (csrc/rt_launch.h)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in (
+        "version", "bytes", "accel", "count", "flat", "mode", "lds", "rows_lds", "block", "grid", "blocks_per_cu", "lpt",
+        "chunks", "head_tiles", "head_chunks", "n_units", "n_block_units", "first_blocks", "isolate_blocks",
+        "lds1_bytes", "oct_bytes", "grid_bytes")]
+        + [(n, ctypes.c_double) for n in ("cull_abs", "cull_rel", "cull_near_t", "cull_near_abs")])
+
+
+assert ctypes.sizeof(LaunchInputs) == 456 and LaunchInputs.small_rmin.offset == 280
+assert ctypes.sizeof(LaunchPlan) == 120 and LaunchPlan.cull_abs.offset == 88
 assert ctypes.sizeof(Sphere) == 80 and Sphere.materialSpecificAttribute.offset == 64
 assert ctypes.sizeof(Scene) == 41024 and Scene.sphereAmount.offset == 40960
 assert ctypes.sizeof(RenderCallInfo) == 64 and RenderCallInfo.camera_dir.offset == 48
@@ -152,6 +190,8 @@ EXPORTS = {
     "rt_debug_util": (_I, [_P, _P]),
     "rt_debug_exact_exhaustive": (_I, [ctypes.c_int, _P]),
     "rt_debug_launch_info": (_I, [_P, _P]),
+    "rt_debug_launch_plan": (_I, [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64]),
+    "rt_debug_row_weights": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, _U32, _P]),
     "rt_debug_kernel_times": (_I, [_P, _P, _U32, ctypes.POINTER(_U32)]),
     "rt_build_info": (ctypes.c_char_p, []),
     "rt_debug_tune": (_I, [_P, ctypes.c_char_p, ctypes.c_double]),

@@ -11,6 +11,10 @@
 //   * the multi-device partition, balancer and frame plan (csrc/rt_plan.cpp): every device count
 //     1-9 over the image heights of the configs and small odd ones, random partitions, random
 //     device times and row weights, malformed inputs;
+//   * the single-device launch plan and the row weights (csrc/rt_launch.cpp): scenes, bands, sample
+//     counts, streams, forms and tuning values of tests/test_launch_plan.py plus the extremes (one
+//     CU, 1x1 and 65535x65535 bands, 0 samples, no spheres, tuning values up to 2^32), every plan
+//     checked against the invariants the kernels rely on;
 //   * the CPU oracle (oracle/rt_oracle.cpp): scenes, small frames in both streams, with a rows map
 //     and accumulation, the tonemap.
 // The geometry contract is driven here too: degenerate finite scenes (negative and
@@ -32,6 +36,7 @@
 #include "../../include/rt_mi355x.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_bvh.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_grid.h"
+#include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_launch.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_plan.h"
 
 extern "C" {
@@ -379,6 +384,125 @@ void check_plans() {
     CHECK(band_parts(2, 10, bad_order, 3).empty());
 }
 
+// The launch plan over the matrix of tests/test_launch_plan.py and the extremes of its domain (what
+// rt_render_device and rt_debug_tune admit), occupancies from a table: every plan keeps the
+// invariants the kernels rely on, or the band is refused as too large.
+void check_launch_plans() {
+    using namespace rt::launch;
+    struct SceneSum { uint32_t n, big, nodes, leaf, grid, gpu, gn[3], cells, refs; float cs[3], rmin, rmax; };
+    const float nan = std::nanf("");
+    const SceneSum scenes[] = {
+        {488, 4, 243, 488, 1, 0, {19, 1, 19}, 361, 836, {1.17204976f, 0.4f, 1.17292404f}, 0.2f, 0.2f},          // configs 2, 3
+        {99860, 4, 67955, 135912, 1, 1, {253, 1, 253}, 64009, 0, {1.25018585f, 0.4f, 1.25017834f}, 0.2f, 0.2f}, // config 5
+        {1028, 4, 529, 1060, 1, 1, {26, 1, 26}, 676, 0, {1.24084449f, 0.4f, 1.23880279f}, 0.2f, 0.2f},         // device tree
+        {0, 0, 0, 0, 0, 0, {0, 0, 0}, 0, 0, {0, 0, 0}, 0.0f, 0.0f},                                            // empty
+        {1, 0, 1, 4, 0, 0, {0, 0, 0}, 0, 0, {0, 0, 0}, 1000.0f, 1000.0f},                                      // one sphere
+        {488, 4, 243, 488, 0, 0, {0, 0, 0}, 0, 0, {0, 0, 0}, 0.2f, 0.2f},                                      // no grid
+        {488, 4, 243, 488, 1, 0, {19, 1, 19}, 361, 836, {1.17204976f, 0.4f, 1.17292404f}, 0.0f, 0.2f},         // r_min 0
+        {488, 4, 243, 488, 1, 0, {19, 1, 19}, 361, 836, {1.17204976f, 0.4f, 1.17292404f}, nan, 0.2f},          // r_min NaN
+        {0xffffffffu, 64, 0xffffffffu, 0xffffffffu, 1, 1, {1, 1, 1}, 0xffffffffu, 0xffffffffu, {1e-30f, 1e30f, 1.0f}, 1e-30f, 1e30f},
+    };
+    const uint32_t bands[][3] = {{8, 8, 0}, {64, 36, 0}, {1920, 135, 1}, {1920, 1080, 0}, {3840, 2160, 0}, {65535, 1, 0},
+                                 {1, 1, 0}, {1, 65535, 1}, {65535, 65535, 0}, {65528, 65535, 1}};
+    const uint32_t spps[] = {0, 1, 2, 7, 100, 1000, 10000, 1u << 19};
+    const uint32_t forms[] = {0, 6, 8, 10, 12, 14, 16, 99};   // 99: brute force
+    const double tunes[] = {Tuning::kUnset, 0.0, 1.0, 7.0, 4096.0, 2147483648.0, 4294967296.0};
+    const uint32_t cus[] = {256, 1};
+    CHECK(tuning_value_ok(-1.0) && tuning_value_ok(0.0) && tuning_value_ok(4294967296.0));
+    CHECK(!tuning_value_ok(4294967297.0) && !tuning_value_ok(1e30) && !tuning_value_ok(INFINITY));
+    CHECK(!tuning_value_ok(-INFINITY) && !tuning_value_ok(nan) && !tuning_value_ok(-0.5));
+    CHECK(tuning_field("nope") == nullptr && tuning_key(kTuningKeys) == nullptr);
+    uint64_t plans = 0, refused = 0;
+    auto run = [&](Inputs& in) {
+        for (uint32_t flat = 0; flat < 2; flat++) {
+            in.flat_grid = flat;
+            Plan p;
+            const char* err = "";
+            const int rc = make_plan(in, table_device(in), p, &err);
+            const uint64_t n_tiles = uint64_t((in.band_w + 7) / 8) * ((in.band_h + 7) / 8);
+            if (rc != RT_OK) {
+                CHECK(rc == RT_ERR_INVALID_ARGUMENT && std::strcmp(err, "band too large") == 0);
+                CHECK(n_tiles * 64u >= (1ull << 32));
+                refused++;
+                continue;
+            }
+            plans++;
+            CHECK(p.chunks >= 1 && p.chunks <= std::max(1u, std::min(in.spp, 4096u)));
+            CHECK(p.head_tiles <= n_tiles);
+            const uint64_t units = 64u * (uint64_t(p.head_tiles) * p.head_chunks + (n_tiles - p.head_tiles) * p.chunks);
+            CHECK(units < (1ull << 32) && p.n_units == units);
+            CHECK(p.n_block_units % 64u == 0 && p.n_block_units <= p.n_units);
+            CHECK(p.first_blocks <= p.n_block_units / 64u);
+            CHECK(p.isolate_blocks <= p.first_blocks);
+            CHECK(!p.head_tiles || p.head_chunks <= p.chunks);
+            CHECK(p.grid >= 1 && p.blocks_per_cu >= 1);
+            CHECK(p.accel >= 1 && p.accel < rt::ACCEL_COUNT && (p.accel == rt::ACCEL_BRUTE) == (in.accel == RT_ACCEL_BRUTE));
+            CHECK(p.rows_lds == rt::kNoRowsLds || (in.has_rows && p.rows_lds % 16u == 0 && p.rows_lds + 4u * in.band_h == p.lds));
+            CHECK(p.lds <= 156u * 1024u);
+            CHECK(p.cull_abs > 0.0 && p.cull_near_abs > 0.0 && p.cull_near_abs <= p.cull_abs);
+        }
+    };
+    for (const SceneSum& sc : scenes)
+        for (const auto& b : bands)
+            for (uint32_t spp : spps)
+                for (uint32_t mode : {uint32_t(RT_RNG_PIXEL_STREAM), uint32_t(RT_RNG_SAMPLE_HASH)})
+                    for (uint32_t form : forms)
+                        for (uint32_t cu : cus)
+                            for (uint32_t lpt = 0; lpt < 2; lpt++) {
+                                Inputs in;
+                                in.bytes = sizeof(in);
+                                in.n_spheres = sc.n; in.n_big = sc.big; in.n_nodes = sc.nodes; in.n_leaf = sc.leaf;
+                                in.has_grid = sc.grid; in.gpu_tree = sc.gpu; in.has_treelet = sc.gpu;
+                                for (int k = 0; k < 3; k++) { in.grid_n[k] = sc.gn[k]; in.grid_cs[k] = sc.cs[k]; }
+                                in.grid_n_cells = sc.cells; in.grid_n_refs = sc.refs;
+                                in.small_rmin = sc.rmin; in.small_rmax = sc.rmax;
+                                in.grid_pad_radius = 2120.0; in.cam_r = 17.29;
+                                in.cu_count = cu;
+                                in.band_w = b[0]; in.band_h = b[1]; in.has_rows = b[2];
+                                in.spp = spp; in.rng_mode = mode; in.lpt_valid = lpt; in.pinhole_lf = 1;
+                                in.accel = form == 99 ? RT_ACCEL_BRUTE : RT_ACCEL_AUTO;
+                                in.reserved1 = form == 99 ? 0 : form;
+                                in.reserved0 = lpt;   // the instrumented build with one of the two
+                                in.block_brute = 256; in.block_walk = 768;
+                                in.n_occ = 3;
+                                in.occ[0] = OccRow{rt::ACCEL_BRUTE, 0xffffffffu, 0, 0xffffffffu, 6};
+                                in.occ[1] = OccRow{0, 0xffffffffu, 0, 65536, 2};
+                                in.occ[2] = OccRow{0, 0xffffffffu, 65537, 0xffffffffu, cu == 1 ? 0u : 1u};   // 0 blocks: planned as 1
+                                run(in);
+                                if (b[0] > 3840 || spp == 7 || form == 6 || form == 10) continue;   // thin the tuning sweep
+                                for (uint32_t k = (spp + form + lpt) % 3; k < kTuningKeys; k += 3)
+                                    for (double tv : tunes) {
+                                        Inputs t = in;
+                                        t.tune.*tuning_field(tuning_key(k)) = tv;
+                                        run(t);
+                                    }
+                            }
+    CHECK(plans > 100000 && refused > 0);
+    {   // an occupancy the table does not answer fails the plan
+        Inputs in;
+        in.band_w = in.band_h = 8;
+        in.block_brute = 256; in.block_walk = 768;
+        Plan p;
+        const char* err = "";
+        CHECK(make_plan(in, table_device(in), p, &err) == RT_ERR_DEVICE);
+    }
+    // row weights: hand-made records (tests/test_launch_plan.py works the answers out), odd shapes
+    std::vector<double> w;
+    const uint32_t cost[] = {1, 2, 3, 4}, order[] = {3, 9, 0, 1};
+    row_weights(cost, order, 4, 2, 16, 2, 5, 2, w);
+    CHECK(w.size() == 16 && w[0] == 0.75 && w[15] == 4.375);
+    row_weights(cost, nullptr, 4, 2, 12, 0, 1, 1, w);
+    CHECK(w.size() == 12 && w[7] == 0.375 && w[8] == 1.75);
+    row_weights(cost, order, 4, 0, 5, 2, 5, 2, w);
+    CHECK(w.size() == 5 && w[4] == 0.0);
+    row_weights(cost, order, 4, 3, 100, 4, 5, 2, w);   // 4 tiles do not fill two rows of 3: the last tile is dropped
+    CHECK(w.size() == 100 && w[8] == 0.0);
+    row_weights(nullptr, nullptr, 0, 7, 9, 0, 1, 1, w);
+    CHECK(w.size() == 9 && w[0] == 0.0);
+    row_weights(nullptr, nullptr, 0, 0, 0, 0, 0, 0, w);
+    CHECK(w.empty());
+}
+
 void check_oracle() {
     const std::vector<Sphere> s = scene(0.0f, 11);
     const uint32_t W = 32, H = 18;
@@ -449,6 +573,7 @@ int main() {
         CHECK(gi.n_cells > 0 && bound >= 99856);
     }
     check_plans();
+    check_launch_plans();
     check_oracle();
     std::printf("sanitize harness: %d checks passed (ASan + UBSan)\n", g_checks);
     return 0;

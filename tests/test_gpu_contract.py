@@ -281,3 +281,37 @@ def test_launch_time_and_row_weights(rtvk, torch, oracle):
             r.launch_row_weights(H + 1, 0)   # not that launch's band height
     finally:
         r.close()
+
+
+LAUNCH_FORMS = {1: "brute", 2: "lbvh-global", 3: "lbvh-lds", 4: "lbvh-octant-lds", 5: "lbvh-treelet", 6: "grid-lds",
+                7: "grid-global", 8: "grid-lds-coop", 9: "grid-global-coop", 10: "grid-lds-rec", 11: "grid-lds-cq",
+                12: "grid-lds-rec-cq"}
+
+
+def test_launch_plan_is_what_ran(rtvk, renderer, torch, oracle):
+    """The plan a launch ran with is the plan its exported inputs give (rt_debug_launch_plan with the
+    context, then without): nothing patches a plan field after planning, and the exported inputs,
+    with the occupancies the launch queried, are complete. The canonical scene at 64x36, 4 and 64
+    spp in both streams through the grid, the octant LBVH (form 8) and brute force, and one 27-row
+    launch with a rows map at 7 spp in the hash stream; the second launch of each pair runs in the
+    LPT order of the first. launch_info()'s words agree with the plan."""
+    W, H = 64, 36
+    sc = oracle.generate_scene()
+    runs = [(W, H, None, spp, rng, accel) for spp in (4, 64) for rng in (HASH, STREAM) for accel in (GRID, LBVH_OCT, 1)]
+    runs.append((W, 27, np.arange(27, dtype=np.uint32) + 5, 7, HASH, GRID))
+    for bw, bh, rows, spp, rng, accel in runs:
+        rci = oracle.render_call_info(spp, W, H)
+        for again in (0, 1):
+            gpu_render(rtvk, renderer, torch, sc, rci, bw, bh, rows=rows, accel=accel, rng_mode=rng)
+            inputs, plan = renderer.launch_plan()
+            what = (bw, bh, spp, rng, accel, again)
+            assert (inputs.band_w, inputs.band_h, inputs.spp, inputs.rng_mode) == (bw, bh, spp, rng), what
+            assert inputs.has_rows == (rows is not None) and inputs.n_spheres == 488
+            assert rtvk.struct_dict(rtvk.launch_plan(inputs)) == rtvk.struct_dict(plan), what
+            info = renderer.launch_info()
+            assert info["form"] == LAUNCH_FORMS[plan.accel], what
+            assert info["chunks"] == plan.chunks and info["lds_bytes"] == plan.lds, what
+            assert info["head_chunks"] == (plan.head_chunks if plan.head_tiles else None), what
+            assert info["flat_grid"] == bool(plan.flat) and info["pinhole_origin"] == bool(inputs.pinhole_lf), what
+            assert info["cus"] == inputs.cu_count
+            assert (plan.accel == 1) == (accel == 1) and plan.mode == (1 if rng == HASH else 0)
