@@ -310,6 +310,37 @@ int rt_multi_set_scene(rt_multi* m, const Sphere* spheres, uint32_t count);
  */
 int rt_multi_render(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt,
                     float* accum_rgba32f, uint8_t* out_rgba8, void* stream);
+/*
+ * One adaptive frame of the whole image over the devices (rci->offset ignored, global seeds): the
+ * N-device form of rt_render_adaptive_device, equal to its one-device frame bit for bit
+ * (accumulator, rgba8, counts and info). opt and ad follow rt_render_adaptive_device's rules
+ * (RT_RNG_SAMPLE_HASH, accumulate 0, even counts, threshold in [0, 16]); every refusal comes
+ * before any render work is queued; RT_ERR_NO_SCENE before rt_multi_set_scene.
+ * The image is dealt as whole 8-row tile rows (rt_partition_tile_rows: the criterion is per 8x8
+ * tile), tile row k on device k % n, statically: adaptive frames are not re-dealt, add nothing to
+ * the balancer's history and leave the plain frames' partition and buffers alone. Device d renders
+ * its part on the context its plain frames use, with its own rows map; its tiles converge on that
+ * device alone. One host thread drives every device: a device's next pass is issued as soon as
+ * that device's own small readback has landed (the per-context events are polled, the thread
+ * yields between polls), so the devices do not move in lock step. Then one RCCL group brings each
+ * remote part's float4 accumulator rows and its per-tile count table (ceil(W/8) * ceil(rows/8)
+ * 32-bit words) to device 0 (device 0's own part never goes through RCCL), and one fused kernel
+ * per part stores accumulator, rgba8 = unorm8(sqrt(sum / float(n))) and the optional counts at
+ * their rows: no row scatter and no whole-image resolve. One device, or device 0 holding every
+ * row: rt_render_adaptive_device straight into the caller's buffers.
+ *   accum_rgba32f / out_rgba8 / sample_count (optional, W*H uint32): DEVICE pointers on device 0.
+ *   info (optional): the frame's totals: passes = the maximum over the devices, tiles,
+ *   tiles_capped and samples = the sums.
+ * Synchronisation as rt_render_adaptive_device: the host blocks on the per-pass readbacks only,
+ * the call returns once the final stores are queued, the outputs are valid after `stream`
+ * completes. The frame plan is rt_debug_multi_plan_adaptive's (include/rt_mi355x_debug.h).
+ */
+int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt,
+                             const rt_adaptive* ad, float* accum_rgba32f, uint8_t* out_rgba8,
+                             uint32_t* sample_count, rt_adaptive_info* info, void* stream);
+/* The last adaptive frame's numbers of one device (the imbalance the static deal leaves); zeros
+ * for a device that rendered nothing. */
+int rt_multi_adaptive_device_info(const rt_multi* m, uint32_t device, rt_adaptive_info* out);
 /* Sum over the devices of the last frame's statistics (synchronises). */
 int rt_multi_stats(rt_multi* m, rt_stats* out);
 /* {devices, ranks of the RCCL communicator (ncclCommCount; 0 for one device: no communicator),
@@ -335,6 +366,12 @@ int rt_multi_partition(const rt_multi* m, uint32_t* rows, uint32_t* counts, uint
  * device d; every device holds floor(height / n) or ceil(height / n) rows (the reference gives the
  * remainder to the first band, src/ray_trace.cpp:74-81). */
 int rt_partition_strips(uint32_t n_devices, uint32_t height, uint32_t* rows, uint32_t* counts);
+/* rt_partition_tile_rows: the static partition of adaptive frames (rt_multi_render_adaptive), same
+ * layout and error rules. The T = ceil(height / 8) tile rows [8k, min(8k + 8, height)) are dealt
+ * round robin, tile row k on device k % n; each device's rows ascend and the ragged last tile row
+ * is globally last, so band tile row j of a device is exactly one global tile row. A device beyond
+ * T gets count 0. */
+int rt_partition_tile_rows(uint32_t n_devices, uint32_t height, uint32_t* rows, uint32_t* counts);
 /* One balancing step (src/workload_tuner.hpp:38-104, without its random moves and without the
  * teardown, src/ray_trace.cpp:774): with a measurement (meas_rows / meas_counts: the partition a
  * frame ran with, meas_ms: each device's trace-kernel ms of that frame; all three NULL for none),

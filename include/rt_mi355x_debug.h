@@ -124,6 +124,14 @@ int rt_debug_multi_plan(uint32_t n_devices, uint32_t width, uint32_t height, con
 int rt_debug_multi_plan_rows(uint32_t n_devices, uint32_t width, uint32_t height, const uint32_t* rows,
                              const uint32_t* counts, uint32_t accumulate, uint32_t* out, uint64_t capacity,
                              uint64_t* count);
+/* The plan of an adaptive frame (rt_multi_render_adaptive) over rt_partition_tile_rows' parts, same
+ * flat form (a device without a tile row has no part). Ops: 9 adaptive render (flags bit 0:
+ * straight into the caller's buffers; the parts' passes are interleaved), 2 / 5 the group, 3 / 4
+ * send / receive of a part's accumulator rows (floats), 10 / 11 send / receive of its per-tile
+ * sample counts (32-bit words), 12 the fused store of a part (accumulator, rgba8, counts; count =
+ * floats). No op 8: there is no whole-image resolve. */
+int rt_debug_multi_plan_adaptive(uint32_t n_devices, uint32_t width, uint32_t height, uint32_t* out,
+                                 uint64_t capacity, uint64_t* count);
 /* Tests on a one-GPU box: an rt_multi of n_devices LOGICAL devices, all on device 0 (one context
  * and one stream each), executing the same frame plans as rt_multi_create's, with every RCCL
  * send / receive pair of a group replaced by one device copy on the receiver's stream, ordered

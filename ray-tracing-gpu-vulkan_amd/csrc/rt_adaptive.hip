@@ -1,7 +1,9 @@
 // rt_adaptive.hip — the kernels of adaptive frames (rt_render_adaptive_device)
 // beside the trace kernels: the per-tile noise estimate that builds the next pass's tile list, and
 // the resolve with per-tile divisors. Both stream the two fixed-point half-buffers A and B (3 u64
-// planes each, TraceParams::fixed layout) once: 48 B per texel, HBM-bound.
+// planes each, TraceParams::fixed layout) once: 48 B per texel, HBM-bound. A third kernel is the
+// store of a multi-device adaptive frame on device 0 (rt_multi_render_adaptive): a part's resolved
+// band and its count table into the full image.
 #include <hip/hip_runtime.h>
 
 #include "rt_adaptive.h"
@@ -83,7 +85,47 @@ __global__ __launch_bounds__(256) void rt_adaptive_resolve_kernel(unsigned long 
     }
 }
 
+// The store of a multi-device adaptive frame (rt_multi_render_adaptive), on device 0, once per part:
+// band row y of `src` (the part's resolved float4 sums, n_rows x width) goes to image row rows[y]
+// of the accumulator, the rgba8 image and the optional count map, tonemapped with the count of the
+// texel's band tile, in rt_adaptive_resolve_kernel's arithmetic (the same float sum, float(cnt),
+// unorm8). One pass over the part instead of a row scatter and a whole-image resolve. The eight
+// texels of a tile row share one count word. Map entries >= dst_rows are skipped.
+__global__ __launch_bounds__(256) void rt_adaptive_store_tiles_kernel(const float4* __restrict__ src, uint64_t n,
+                                                                      uint32_t width, uint32_t tiles_x,
+                                                                      const uint32_t* __restrict__ tile_n,
+                                                                      const uint32_t* __restrict__ rows,
+                                                                      uint32_t dst_rows, float4* __restrict__ accum,
+                                                                      uint32_t* __restrict__ out,
+                                                                      uint32_t* __restrict__ sample_count) {
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t y = uint32_t(i) / width, x = uint32_t(i) - y * width;   // n < 2^32 (band sides < 2^16)
+        const uint32_t dy = rows[y];
+        if (dy >= dst_rows) continue;
+        const uint32_t cnt = tile_n[(y >> 3) * tiles_x + (x >> 3)];
+        const float4 s = src[i];
+        const size_t d = size_t(dy) * width + x;
+        accum[d] = s;
+        const float spp = float(cnt);
+        out[d] = unorm8(__builtin_sqrtf(s.x / spp)) | (unorm8(__builtin_sqrtf(s.y / spp)) << 8) |
+                 (unorm8(__builtin_sqrtf(s.z / spp)) << 16) | (255u << 24);
+        if (sample_count) sample_count[d] = cnt;
+    }
+}
+
 namespace rt {
+
+hipError_t launch_adaptive_store_tiles(const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
+                                       const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out,
+                                       uint32_t* sample_count, hipStream_t st) {
+    const uint64_t n_texels = uint64_t(n_rows) * width;
+    if (n_texels == 0) return hipSuccess;
+    const uint64_t need = (n_texels + 255) / 256;
+    hipLaunchKernelGGL(rt_adaptive_store_tiles_kernel, dim3(uint32_t(need < 8192 ? need : 8192)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(src), n_texels, width, (width + 7u) / 8u, tile_n, rows, dst_rows,
+                       reinterpret_cast<float4*>(accum), reinterpret_cast<uint32_t*>(out), sample_count);
+    return hipGetLastError();
+}
 
 hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st) {
     return hipMemsetAsync(state, 0, sizeof(AdaptiveState), st);

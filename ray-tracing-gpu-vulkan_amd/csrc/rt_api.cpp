@@ -52,6 +52,9 @@ hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);
 hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
                                    uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
                                    uint32_t* sample_count, hipStream_t st);
+hipError_t launch_adaptive_store_tiles(const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
+                                       const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out,
+                                       uint32_t* sample_count, hipStream_t st);
 }  // namespace rt
 
 using rt::launch::Tuning;
@@ -66,6 +69,17 @@ struct SceneSlot {
     hipEvent_t ev_free = nullptr;     // recorded after every launch that reads this arena
     bool used = false;                // ev_free has been recorded
 };
+
+namespace {
+// The launch parameters rt_render_device and rt_render_adaptive_device share: everything that
+// does not depend on how the band's samples are split into units.
+struct TraceSetup {
+    rt::TraceParams P;
+    rt::launch::Inputs in;       // what the plan is computed from
+    rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
+    uint64_t tiles_x = 0, n_tiles = 0;
+};
+}  // namespace
 
 struct rt_context {
     int device = 0;
@@ -174,6 +188,20 @@ struct rt_context {
         rt::AdaptiveState* state = nullptr;     // device
         rt::AdaptiveState* host = nullptr;      // pinned copy, read after `ev` once per pass
         hipEvent_t ev = nullptr;
+        // The frame in flight, between rt::adaptive_begin and rt::adaptive_finish / adaptive_abort
+        // (rt_host.h): the pass loop as a state machine, so that one host thread can interleave
+        // the passes of several contexts (rt_multi_render_adaptive).
+        struct Frame {
+            bool open = false;
+            bool pending = false;               // a pass is issued and its readback not yet consumed
+            TraceSetup S;
+            rt_options o{};
+            rt_adaptive ad{};
+            hipStream_t st = nullptr;
+            uint32_t max_spp = 0, done = 0, passes = 0, cur = 0;
+            uint64_t active = 0;                // tiles of the next pass
+            const uint32_t* list = nullptr;     // their list (null: pass 0, every tile, row-major)
+        } frame;
     } adaptive;
 };
 
@@ -989,15 +1017,6 @@ int scene_call(rt_context* ctx, const Sphere* spheres, uint32_t count, bool devi
     return scene_done(ctx, rc);
 }
 
-// The launch parameters rt_render_device and rt_render_adaptive_device share: everything that
-// does not depend on how the band's samples are split into units.
-struct TraceSetup {
-    rt::TraceParams P;
-    rt::launch::Inputs in;       // what the plan is computed from
-    rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
-    uint64_t tiles_x = 0, n_tiles = 0;
-};
-
 // The kernels' translation unit as the plan sees it (rt_launch.h Device; user = a PlanDevice). The
 // launch's own occupancy query goes through the per-context cache; every answer is noted in the
 // inputs, which rt_debug_launch_plan exports.
@@ -1277,85 +1296,228 @@ int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStre
     return RT_OK;
 }
 
-// The passes of an adaptive frame and its resolve. A failure after the first
-// launch leaves sums in the half-buffers: the caller clears them.
-int adaptive_passes(rt_context* ctx, TraceSetup& S, const rt_options& o, const rt_adaptive& ad, uint32_t max_spp,
-                    float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info, hipStream_t st) {
+// The half-buffers and tile tables of the frame in flight.
+struct AdaptiveBuffers {
+    uint64_t texels, n_tiles;
+    unsigned long long* half[2];
+    uint32_t* tile_n;
+    uint32_t* lists[2];
+};
+AdaptiveBuffers adaptive_buffers(rt_context* ctx) {
     rt_context::Adaptive& a = ctx->adaptive;
-    rt::TraceParams& P = S.P;
-    const uint64_t texels = uint64_t(P.band_w) * P.band_h, n_tiles = S.n_tiles;
-    unsigned long long* half[2] = {a.planes, a.planes + 3u * texels};
-    uint32_t* tile_n = a.tiles;
-    uint32_t* lists[2] = {a.tiles + n_tiles, a.tiles + 2u * n_tiles};
+    const rt::TraceParams& P = a.frame.S.P;
+    AdaptiveBuffers b;
+    b.texels = uint64_t(P.band_w) * P.band_h;
+    b.n_tiles = a.frame.S.n_tiles;
+    b.half[0] = a.planes;
+    b.half[1] = a.planes + 3u * b.texels;
+    b.tile_n = a.tiles;
+    b.lists[0] = a.tiles + b.n_tiles;
+    b.lists[1] = a.tiles + 2u * b.n_tiles;
+    return b;
+}
+
+}  // namespace
+
+// The adaptive pass loop as steps on a context (rt_host.h).
+namespace rt {
+
+int adaptive_check_values(const RenderCallInfo* rci, const rt_options& o, const rt_adaptive* ad, const char* who) {
+    if (!ad) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive is NULL");
+    const uint32_t max_spp = rci->samplesPerRenderCall;
+    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
+    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
+    if (ad->min_spp == 0 || (ad->min_spp & 1u)) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp must be even and >= 2");
+    if (ad->step_spp == 0 || (ad->step_spp & 1u))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive step_spp must be even and >= 2");
+    if (max_spp == 0 || (max_spp & 1u))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive max_spp (samplesPerRenderCall) must be even and >= 2");
+    if (ad->min_spp > max_spp) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp exceeds max_spp (samplesPerRenderCall)");
+    if (uint64_t(o.sample_base) + max_spp > 0xffffffffull)
+        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + max_spp overflows 32 bits");
+    if (!(std::isfinite(ad->threshold) && ad->threshold >= 0.0f && ad->threshold <= 16.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive threshold must be finite and within [0, 16]");
+    if (ad->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive reserved must be 0");
+    return RT_OK;
+}
+
+int adaptive_check(const rt_context* ctx, const RenderCallInfo* rci, uint32_t band_width, uint32_t band_height,
+                   const float* accum, const uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
+                   const char* who, rt_options* o_out, bool* empty) {
+    rt_options o;
+    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, empty)) return rc;
+    if (*empty) return RT_OK;
+    if (int rc = adaptive_check_values(rci, o, ad, who)) return rc;
+    if (o_out) *o_out = o;
+    return RT_OK;
+}
+
+int adaptive_abort(rt_context* ctx, int rc) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    if (!a.frame.open) return rc;
+    DeviceGuard g(ctx->device);
+    const std::string msg = rt::g_last_error;   // the half-buffers are zero between calls, whatever happened
+    (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), a.frame.st);
+    rt::g_last_error = msg;
+    a.frame.open = a.frame.pending = false;
+    if (int rc2 = render_issued(ctx, a.frame.st)) return rc ? rc : rc2;
+    return rc;
+}
+
+int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                   uint32_t band_height, float* accum, uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
+                   void* stream, const char* who, bool* open) {
+    *open = false;
+    rt_options o;
+    bool empty = false;
+    if (int rc = adaptive_check(ctx, rci, band_width, band_height, accum, out, opt, ad, who, &o, &empty)) return rc;
+    if (empty) return RT_OK;
+    rt_context::Adaptive& a = ctx->adaptive;
+    rt_context::Adaptive::Frame& f = a.frame;
+    if (f.open) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is in flight on this context");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;
+    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, f.S)) return rc;
+    if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, f.S.n_tiles, st)) return rc;
+    rt::TraceParams& P = f.S.P;
     // the walk kernels record tile costs unconditionally (rt_kernels.hip record_tile_cost): a
     // scratch table of the whole tile grid, never read
-    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * n_tiles : nullptr;
+    P.tile_cost = f.S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * f.S.n_tiles : nullptr;
     P.accumulate = 0u;
     P.head_tiles = 0u;
-    RT_HIP(rt::launch_adaptive_init(a.state, st));
-    const uint32_t thr_q16 = rt::adaptive_thr_q16(ad.threshold);
-    uint32_t done = 0, passes = 0, cur = 0;
-    uint64_t active = n_tiles;
-    const uint32_t* list = nullptr;   // pass 0: every tile, row-major
-    while (active) {
-        const uint32_t k = passes == 0 ? ad.min_spp : std::min(ad.step_spp, max_spp - done);
-        for (uint32_t h = 0; h < 2; h++) {   // samples [done, done + k/2) into A, the next k/2 into B
-            P.spp = k / 2u;
-            P.sample_base = o.sample_base + done + h * (k / 2u);
-            P.fixed = half[h];
-            P.tile_order = list;
-            // uniform chunks by rt_render_device's rule for the pixels of the list; no head / tail
-            // split (the list carries no cost order)
-            const char* err = "";
-            if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * active, active, list != nullptr, false, &err))
-                return fail(rc, err);
-            P.chunks = S.plan.chunks;
-            P.head_chunks = S.plan.head_chunks;
-            P.n_units = S.plan.n_units;
-            if (int rc = launch_units(ctx, S, st)) return rc;
-        }
-        done += k;
-        rt::AdaptiveErrorParams K;
-        std::memset(&K, 0, sizeof(K));
-        K.a = half[0];
-        K.b = half[1];
-        K.texels = texels;
-        K.band_w = P.band_w;
-        K.band_h = P.band_h;
-        K.tiles_x = P.tiles_x;
-        K.list = list;
-        K.n_list = uint32_t(active);
-        K.n_done = done;
-        K.max_spp = max_spp;
-        K.thr_q16 = thr_q16;
-        K.cur = cur;
-        K.tile_n = tile_n;
-        K.next_list = lists[cur ^ 1u];
-        K.state = a.state;
-        RT_HIP(rt::launch_adaptive_error(K, st));
-        // the one host wait of the pass: the next list's length (and the running totals)
-        RT_HIP(hipMemcpyAsync(a.host, a.state, sizeof(rt::AdaptiveState), hipMemcpyDeviceToHost, st));
-        RT_HIP(hipEventRecord(a.ev, st));
-        RT_HIP(hipEventSynchronize(a.ev));
-        passes++;
-        cur ^= 1u;
-        active = a.host->count[cur];
-        list = lists[cur];
-        if (active > n_tiles) return fail(RT_ERR_DEVICE, "adaptive tile list longer than the tile grid");
+    f.o = o;
+    f.ad = *ad;
+    f.st = st;
+    f.max_spp = rci->samplesPerRenderCall;
+    f.done = f.passes = f.cur = 0;
+    f.active = f.S.n_tiles;
+    f.list = nullptr;   // pass 0: every tile, row-major
+    f.pending = false;
+    f.open = true;      // from here on a failure leaves sums or state behind: adaptive_abort clears them
+    if (hipError_t e = rt::launch_adaptive_init(a.state, st); e != hipSuccess)
+        return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_init: ") + hipGetErrorString(e)));
+    *open = true;
+    return RT_OK;
+}
+
+bool adaptive_active(const rt_context* ctx) { return ctx->adaptive.frame.open && ctx->adaptive.frame.active != 0; }
+
+int adaptive_issue_pass(rt_context* ctx) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    rt_context::Adaptive::Frame& f = a.frame;
+    if (!f.open || f.pending || !f.active) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive pass out of order");
+    DeviceGuard g(ctx->device);
+    const AdaptiveBuffers b = adaptive_buffers(ctx);
+    TraceSetup& S = f.S;
+    rt::TraceParams& P = S.P;
+    hipStream_t st = f.st;
+    const uint32_t k = f.passes == 0 ? f.ad.min_spp : std::min(f.ad.step_spp, f.max_spp - f.done);
+    for (uint32_t h = 0; h < 2; h++) {   // samples [done, done + k/2) into A, the next k/2 into B
+        P.spp = k / 2u;
+        P.sample_base = f.o.sample_base + f.done + h * (k / 2u);
+        P.fixed = b.half[h];
+        P.tile_order = f.list;
+        // uniform chunks by rt_render_device's rule for the pixels of the list; no head / tail
+        // split (the list carries no cost order)
+        const char* err = "";
+        if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * f.active, f.active, f.list != nullptr, false, &err))
+            return fail(rc, err);
+        P.chunks = S.plan.chunks;
+        P.head_chunks = S.plan.head_chunks;
+        P.n_units = S.plan.n_units;
+        if (int rc = launch_units(ctx, S, st)) return rc;
     }
-    RT_HIP(rt::launch_adaptive_resolve(half[0], half[1], texels, P.band_w, P.tiles_x, tile_n, accum, out, sample_count,
-                                       st));
+    f.done += k;
+    rt::AdaptiveErrorParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.a = b.half[0];
+    K.b = b.half[1];
+    K.texels = b.texels;
+    K.band_w = P.band_w;
+    K.band_h = P.band_h;
+    K.tiles_x = P.tiles_x;
+    K.list = f.list;
+    K.n_list = uint32_t(f.active);
+    K.n_done = f.done;
+    K.max_spp = f.max_spp;
+    K.thr_q16 = rt::adaptive_thr_q16(f.ad.threshold);
+    K.cur = f.cur;
+    K.tile_n = b.tile_n;
+    K.next_list = b.lists[f.cur ^ 1u];
+    K.state = a.state;
+    RT_HIP(rt::launch_adaptive_error(K, st));
+    // the one readback of the pass: the next list's length (and the running totals)
+    RT_HIP(hipMemcpyAsync(a.host, a.state, sizeof(rt::AdaptiveState), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipEventRecord(a.ev, st));
+    f.pending = true;
+    return RT_OK;
+}
+
+int adaptive_pass_done(rt_context* ctx, bool block, bool* done) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    rt_context::Adaptive::Frame& f = a.frame;
+    if (done) *done = false;
+    if (!f.open || !f.pending) return fail(RT_ERR_INVALID_ARGUMENT, "no adaptive pass in flight");
+    DeviceGuard g(ctx->device);
+    if (block) {
+        RT_HIP(hipEventSynchronize(a.ev));
+    } else {
+        const hipError_t e = hipEventQuery(a.ev);
+        if (e == hipErrorNotReady) {
+            (void)hipGetLastError();   // not an error: nothing for a later launch check to pick up
+            return RT_OK;
+        }
+        RT_HIP(e);
+    }
+    const AdaptiveBuffers b = adaptive_buffers(ctx);
+    f.pending = false;
+    f.passes++;
+    f.cur ^= 1u;
+    f.active = a.host->count[f.cur];
+    f.list = b.lists[f.cur];
+    if (f.active > b.n_tiles) return fail(RT_ERR_DEVICE, "adaptive tile list longer than the tile grid");
+    if (done) *done = true;
+    return RT_OK;
+}
+
+int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    rt_context::Adaptive::Frame& f = a.frame;
+    if (!f.open || f.pending || f.active) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive finish out of order");
+    DeviceGuard g(ctx->device);
+    const AdaptiveBuffers b = adaptive_buffers(ctx);
+    const rt::TraceParams& P = f.S.P;
+    if (hipError_t e = rt::launch_adaptive_resolve(b.half[0], b.half[1], b.texels, P.band_w, P.tiles_x, b.tile_n, accum,
+                                                   out, sample_count, f.st);
+        e != hipSuccess)
+        return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
     if (info) {
-        info->passes = passes;
-        info->tiles = uint32_t(n_tiles);
+        info->passes = f.passes;
+        info->tiles = uint32_t(b.n_tiles);
         info->tiles_capped = a.host->capped;
         info->reserved = 0;
         info->samples = a.host->samples;
     }
+    f.open = false;
+    return render_issued(ctx, f.st);
+}
+
+const uint32_t* adaptive_tile_counts(const rt_context* ctx) { return ctx->adaptive.tiles; }
+
+int adaptive_store_tiles(int device, const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
+                         const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out, uint32_t* sample_count,
+                         void* stream) {
+    if (n_rows == 0 || width == 0) return RT_OK;
+    if (!src || !tile_n || !rows || !accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard g(device);
+    RT_HIP(rt::launch_adaptive_store_tiles(src, n_rows, width, tile_n, rows, dst_rows, accum, out, sample_count,
+                                           static_cast<hipStream_t>(stream)));
     return RT_OK;
 }
 
-}  // namespace
+}  // namespace rt
 
 extern "C" {
 
@@ -1483,42 +1645,19 @@ int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const 
                               uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
                               rt_adaptive_info* info, void* stream) {
     if (info) std::memset(info, 0, sizeof(*info));
-    rt_options o;
-    bool empty = false;
-    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, "rt_render_adaptive_device", o,
-                                   &empty))
+    // the state machine of rt_host.h, one context: each pass waits for its own readback
+    bool open = false;
+    if (int rc = rt::adaptive_begin(ctx, rci, rows, band_width, band_height, accum, out, opt, ad, stream,
+                                    "rt_render_adaptive_device", &open))
         return rc;
-    if (empty) return RT_OK;
-    if (!ad) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive is NULL");
-    const uint32_t max_spp = rci->samplesPerRenderCall;
-    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_device needs rng_mode RT_RNG_SAMPLE_HASH");
-    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_adaptive_device: accumulate must be 0");
-    if (ad->min_spp == 0 || (ad->min_spp & 1u)) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp must be even and >= 2");
-    if (ad->step_spp == 0 || (ad->step_spp & 1u))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive step_spp must be even and >= 2");
-    if (max_spp == 0 || (max_spp & 1u))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive max_spp (samplesPerRenderCall) must be even and >= 2");
-    if (ad->min_spp > max_spp) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp exceeds max_spp (samplesPerRenderCall)");
-    if (uint64_t(o.sample_base) + max_spp > 0xffffffffull)
-        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + max_spp overflows 32 bits");
-    if (!(std::isfinite(ad->threshold) && ad->threshold >= 0.0f && ad->threshold <= 16.0f))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive threshold must be finite and within [0, 16]");
-    if (ad->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive reserved must be 0");
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;
-    TraceSetup S;
-    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
-    if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, S.n_tiles, st)) return rc;
-    int rc = adaptive_passes(ctx, S, o, *ad, max_spp, accum, out, sample_count, info, st);
-    if (rc != RT_OK) {   // the half-buffers are zero between calls, whatever happened
-        const std::string msg = rt::g_last_error;
-        (void)hipMemsetAsync(ctx->adaptive.planes, 0, ctx->adaptive.cap * 6u * sizeof(unsigned long long), st);
-        rt::g_last_error = msg;
+    if (!open) return RT_OK;   // a band without texels
+    int rc = RT_OK;
+    while (rc == RT_OK && rt::adaptive_active(ctx)) {
+        rc = rt::adaptive_issue_pass(ctx);
+        if (rc == RT_OK) rc = rt::adaptive_pass_done(ctx, true, nullptr);
     }
-    if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
-    return rc;
+    if (rc != RT_OK) return rt::adaptive_abort(ctx, rc);
+    return rt::adaptive_finish(ctx, accum, out, sample_count, info);
 }
 
 int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, int* converged) {

@@ -35,6 +35,47 @@ int launch_ms_at(rt_context* ctx, uint64_t index, float* ms);
 int launch_row_weights(rt_context* ctx, uint64_t index, std::vector<double>& w);
 void keep_row_weights(rt_context* ctx);
 
+// The pass loop of an adaptive frame (rt_render_adaptive_device) as resumable
+// steps on a context, so that one host thread interleaves the passes of several contexts
+// (rt_multi_render_adaptive); rt_render_adaptive_device itself is a loop over them. (Here and not
+// in rt_internal.h: that header is compiled into the trace kernels' object.)
+//   adaptive_check  the argument checks alone, no device work: rt_render_adaptive_device's rules,
+//                   `who` names the caller in messages. *empty: a band without texels.
+//   adaptive_check_values  the part of them that needs no context (options, adaptive, the cap).
+//   adaptive_begin  the checks, the buffers and the state reset, ordered on `stream`. *open = false
+//                   and RT_OK: nothing to render. accum / out: the band buffers finish will write.
+//   adaptive_active the frame is open and tiles are left for another pass.
+//   adaptive_issue_pass  two trace launches, the error kernel, the readback of the next list's
+//                   length and its event. No host wait.
+//   adaptive_pass_done   has that readback landed? block = false: hipEventQuery (*done = false
+//                   when not yet); block = true waits. Consumes it once landed: the next pass's list.
+//   adaptive_finish the resolve into accum / out / sample_count (band layout; sample_count optional),
+//                   fills info (optional) and closes the frame.
+//   adaptive_abort  after a failed step: clears the half-buffers (A and B are zero between calls,
+//                   whatever happened) and closes the frame; returns rc (or the closing's own error).
+//   adaptive_tile_counts  DEVICE pointer of the band's per-tile sample counts (ceil(W / 8) x
+//                   ceil(rows / 8) words, row-major), written by the frame's passes on its stream;
+//                   valid until the context's next adaptive call.
+int adaptive_check_values(const RenderCallInfo* rci, const rt_options& o, const rt_adaptive* ad, const char* who);
+int adaptive_check(const rt_context* ctx, const RenderCallInfo* rci, uint32_t band_width, uint32_t band_height,
+                   const float* accum, const uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
+                   const char* who, rt_options* o_out, bool* empty);
+int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                   uint32_t band_height, float* accum, uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
+                   void* stream, const char* who, bool* open);
+bool adaptive_active(const rt_context* ctx);
+int adaptive_issue_pass(rt_context* ctx);
+int adaptive_pass_done(rt_context* ctx, bool block, bool* done);
+int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info);
+int adaptive_abort(rt_context* ctx, int rc);
+const uint32_t* adaptive_tile_counts(const rt_context* ctx);
+// The fused store of a multi-device adaptive frame on `device` (rt_adaptive.hip
+// rt_adaptive_store_tiles_kernel): band rows of `src` with the part's count table into rows[i] of
+// the image's accumulator, rgba8 and optional count map.
+int adaptive_store_tiles(int device, const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
+                         const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out, uint32_t* sample_count,
+                         void* stream);
+
 // Message of the calling thread's last failure (rt_last_error()).
 extern thread_local std::string g_last_error;
 int fail(int code, const std::string& msg);

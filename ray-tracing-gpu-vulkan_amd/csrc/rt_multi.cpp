@@ -22,6 +22,13 @@
 // needed) and each band's LPT tile costs stay (rows leave and join at a band's end, so its other
 // tiles keep their index).
 //
+// Adaptive frames (rt_multi_render_adaptive): a static deal of whole 8-row tile
+// rows (rt_plan.h tile_row_parts; the stop criterion is per 8x8 tile), each part rendered on its
+// device's context by the resumable pass loop of rt_host.h, all parts' passes interleaved by the
+// calling thread; the gather adds each part's per-tile count table, and one fused kernel per part
+// stores accumulator, rgba8 and counts in place. They keep their own rows maps and buffers and
+// never touch the balancer.
+//
 // A frame is a FramePlan (rt_plan.h): the partition and the ordered steps rt_multi_render executes.
 // The plan is host-only data, so the CPU tests check it for every device count and height without
 // a GPU (rt_debug_multi_plan*, tests/test_multi_plan.py). rt_debug_multi_create_logical runs the
@@ -40,6 +47,7 @@
 #include <exception>
 #include <memory>
 #include <string>
+#include <thread>
 #include <utility>
 #include <vector>
 
@@ -78,7 +86,22 @@ struct Launch {
     float* stage_acc = nullptr;          // dev != 0: the band's copy on device 0
 };
 
-constexpr uint32_t kMaxLag = 8;   // strip frames the balancer keeps (its largest lag)
+// One part of an adaptive frame (rt_multi_render_adaptive; rt_plan.h tile_row_parts) with its own
+// rows maps and buffers: a plain frame's Launch is never rewritten by an adaptive frame. The part
+// renders on the context of its device's Launch (no second context, no second scene).
+struct AdaptivePart {
+    uint32_t dev = 0;
+    std::vector<uint32_t> rows;          // global rows, band order: whole 8-row tile rows
+    bool whole = false;
+    uint32_t* rows_dev = nullptr;        // rows on dev (the kernel's map)
+    uint32_t* rows_root = nullptr;       // rows on device 0 (the store's map)
+    float* acc = nullptr;                // band on dev: rows x W float4
+    uint8_t* out = nullptr;              // band on dev: rows x W rgba8 (the band resolve's store; not sent)
+    float* stage_acc = nullptr;          // dev != 0: the band's copy on device 0
+    uint32_t* stage_counts = nullptr;    // dev != 0: the band's per-tile counts on device 0
+};
+
+constexpr uint32_t kMaxLag = 8;  // strip frames the balancer keeps (its largest lag)
 
 // A rendered strip frame, for the balancer: its partition and each part's launch index on its
 // context (UINT64_MAX: the part rendered nothing).
@@ -117,6 +140,13 @@ struct rt_multi {
         uint64_t frames = 0, rebalances = 0, moved = 0;
         double predicted = 1.0;          // predicted max / mean after the last re-deal
     } bal;
+    // adaptive frames: their own static partition (never re-dealt, no balancer record) and buffers
+    struct AdaptiveFrames {
+        uint32_t W = 0, H = 0;
+        std::vector<AdaptivePart> parts;         // one per plan part, same index
+        FramePlan plan;
+        std::vector<rt_adaptive_info> info;      // per device, the last adaptive frame
+    } ad;
 };
 
 namespace {
@@ -468,6 +498,254 @@ int run_plan(rt_multi* m, const FramePlan& p, const RenderCallInfo* rcis, size_t
     return rc;
 }
 
+// ---- adaptive frames ---------------------------------------------------------------------------
+
+// The context of logical device `dev`: its Launch's (the strip partition has one per device).
+rt_context* ctx_of(rt_multi* m, uint32_t dev) {
+    for (Launch& l : m->launches)
+        if (l.dev == dev) return l.ctx;
+    return nullptr;
+}
+
+void free_adaptive(rt_multi* m) {
+    for (AdaptivePart& p : m->ad.parts) {
+        {
+            DeviceGuard g(phys_of(m, p.dev));
+            (void)hipDeviceSynchronize();
+            if (p.rows_dev) (void)hipFree(p.rows_dev);
+            if (p.acc) (void)hipFree(p.acc);
+            if (p.out) (void)hipFree(p.out);
+        }
+        DeviceGuard g0(phys_of(m, 0));
+        (void)hipDeviceSynchronize();
+        if (p.rows_root) (void)hipFree(p.rows_root);
+        if (p.stage_acc) (void)hipFree(p.stage_acc);
+        if (p.stage_counts) (void)hipFree(p.stage_counts);
+    }
+    m->ad.parts.clear();
+    m->ad.plan = FramePlan{};
+    m->ad.W = m->ad.H = 0;
+}
+
+// The tile-row parts of a W x H adaptive frame, their buffers and the frame's plan. Same size:
+// nothing to do (the deal is static).
+int set_adaptive_partition(rt_multi* m, uint32_t W, uint32_t H) {
+    if (m->ad.W == W && m->ad.H == H && !m->ad.parts.empty()) return RT_OK;
+    free_adaptive(m);
+    m->ad.plan = make_adaptive_plan(W, H, tile_row_parts(m->n, H));
+    for (const PlanPart& q : m->ad.plan.parts) {
+        AdaptivePart p;
+        p.dev = q.dev;
+        p.rows = q.rows;
+        p.whole = q.whole;
+        m->ad.parts.push_back(std::move(p));
+    }
+    m->ad.W = W;
+    m->ad.H = H;
+    const size_t tiles_x = (size_t(W) + kStrip - 1) / kStrip;
+    for (AdaptivePart& p : m->ad.parts) {
+        const size_t nr = p.rows.size(), texels = nr * W;
+        if (!nr || p.whole) continue;
+        {
+            DeviceGuard g(phys_of(m, p.dev));
+            RT_HIP(hipMalloc(&p.rows_dev, nr * 4));
+            RT_HIP(hipMalloc(&p.acc, texels * 16));
+            RT_HIP(hipMalloc(&p.out, texels * 4));
+            RT_HIP(hipMemcpy(p.rows_dev, p.rows.data(), nr * 4, hipMemcpyHostToDevice));
+        }
+        DeviceGuard g0(phys_of(m, 0));
+        RT_HIP(hipMalloc(&p.rows_root, nr * 4));
+        RT_HIP(hipMemcpy(p.rows_root, p.rows.data(), nr * 4, hipMemcpyHostToDevice));
+        if (p.dev != 0) {
+            RT_HIP(hipMalloc(&p.stage_acc, texels * 16));
+            RT_HIP(hipMalloc(&p.stage_counts, tiles_x * ((nr + kStrip - 1) / kStrip) * 4));
+        }
+    }
+    return RT_OK;
+}
+
+// The passes of every part, interleaved by this one host thread: each device's next pass is issued
+// as soon as that device's own readback has landed (a poll of the per-context events, a yield
+// between rounds without progress), so no device waits for another's pass and none runs its whole
+// frame before the next starts. Every refusal comes before any device work is queued.
+int render_adaptive_parts(rt_multi* m, const std::vector<PlanStep>& renders, const RenderCallInfo* rci,
+                          const rt_options* opt, const rt_adaptive* ad, float* acc, uint8_t* out,
+                          uint32_t* sample_count) {
+    static const char* who = "rt_multi_render_adaptive";
+    const uint32_t W = m->ad.W, H = m->ad.H;
+    RenderCallInfo r = *rci;
+    r.offset = rt_uvec2{0, 0};   // the rows map carries the global rows
+    if (renders.size() == 1 && (renders[0].flags & kDirect)) {   // one device holds every row
+        rt_context* c0 = ctx_of(m, 0);
+        if (!c0) return fail(RT_ERR_INVALID_ARGUMENT, "no context on device 0");
+        return rt_render_adaptive_device(c0, &r, nullptr, W, H, acc, out, sample_count, opt, ad, &m->ad.info[0],
+                                         m->stream[0]);
+    }
+    struct Run {
+        AdaptivePart* p;
+        rt_context* ctx;
+        bool live;
+    };
+    std::vector<Run> runs;
+    for (const PlanStep& s : renders) {
+        AdaptivePart& p = m->ad.parts[s.part];
+        rt_context* c = ctx_of(m, p.dev);
+        if (!c) return fail(RT_ERR_INVALID_ARGUMENT, "no context on a device of the plan");
+        bool empty = false;
+        if (int rc = rt::adaptive_check(c, &r, W, uint32_t(p.rows.size()), p.acc, p.out, opt, ad, who, nullptr, &empty))
+            return rc;
+        runs.push_back(Run{&p, c, false});
+    }
+    auto body = [&]() -> int {
+        for (Run& u : runs) {
+            if (int rc = rt::adaptive_begin(u.ctx, &r, u.p->rows_dev, W, uint32_t(u.p->rows.size()), u.p->acc, u.p->out,
+                                            opt, ad, m->stream[u.p->dev], who, &u.live))
+                return rc;
+        }
+        size_t left = 0;
+        for (Run& u : runs) {
+            if (!u.live) continue;
+            if (int rc = rt::adaptive_issue_pass(u.ctx)) return rc;
+            left++;
+        }
+        while (left) {
+            bool progress = false;
+            for (Run& u : runs) {
+                if (!u.live) continue;
+                bool done = false;
+                if (int rc = rt::adaptive_pass_done(u.ctx, false, &done)) return rc;
+                if (!done) continue;
+                progress = true;
+                if (rt::adaptive_active(u.ctx)) {
+                    if (int rc = rt::adaptive_issue_pass(u.ctx)) return rc;
+                    continue;
+                }
+                // the band's sums and rgba8 in band layout; the counts stay in the context's tile table
+                if (int rc = rt::adaptive_finish(u.ctx, u.p->acc, u.p->out, nullptr, &m->ad.info[u.p->dev])) return rc;
+                u.live = false;
+                left--;
+            }
+            if (!progress) std::this_thread::yield();
+        }
+        return RT_OK;
+    };
+    const int rc = body();
+    if (rc != RT_OK)
+        for (Run& u : runs) (void)rt::adaptive_abort(u.ctx, rc);   // frames still open: A and B cleared
+    return rc;
+}
+
+// A send / receive pair of an adaptive frame's group on the logical transport: as
+// logical_transfers, for the accumulator bands and the count tables.
+int adaptive_logical_transfers(rt_multi* m, const std::vector<PlanStep>& group) {
+    size_t ev = 0;
+    for (const PlanStep& r : group) {
+        if (r.op != OP_RECV && r.op != OP_RECV_COUNTS) continue;
+        const uint32_t send_op = r.op == OP_RECV ? uint32_t(OP_SEND) : uint32_t(OP_SEND_COUNTS);
+        const PlanStep* s = nullptr;
+        for (const PlanStep& c : group)
+            if (c.op == send_op && c.dev == r.peer && c.peer == r.dev && c.part == r.part) s = &c;
+        if (!s || s->count != r.count || r.dev != 0) return fail(RT_ERR_INVALID_ARGUMENT, "unpaired receive in the plan");
+        AdaptivePart& p = m->ad.parts[r.part];
+        const void* src = r.op == OP_RECV ? static_cast<const void*>(p.acc)
+                                          : static_cast<const void*>(rt::adaptive_tile_counts(ctx_of(m, p.dev)));
+        void* dst = r.op == OP_RECV ? static_cast<void*>(p.stage_acc) : static_cast<void*>(p.stage_counts);
+        while (m->xev.size() < ev + 2) {
+            hipEvent_t e = nullptr;
+            DeviceGuard g(phys_of(m, 0));
+            RT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            m->xev.push_back(e);
+        }
+        DeviceGuard g(phys_of(m, r.dev));
+        RT_HIP(hipEventRecord(m->xev[ev], m->stream[s->dev]));
+        RT_HIP(hipStreamWaitEvent(m->stream[r.dev], m->xev[ev], 0));
+        RT_HIP(hipMemcpyAsync(dst, src, r.count * 4, hipMemcpyDeviceToDevice, m->stream[r.dev]));
+        RT_HIP(hipEventRecord(m->xev[ev + 1], m->stream[r.dev]));
+        RT_HIP(hipStreamWaitEvent(m->stream[s->dev], m->xev[ev + 1], 0));
+        ev += 2;
+    }
+    return RT_OK;
+}
+
+// Executes an adaptive frame's plan (make_adaptive_plan) into the caller's buffers on device 0.
+int run_adaptive_plan(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, const rt_adaptive* ad,
+                      float* acc, uint8_t* out, uint32_t* sample_count) {
+    const FramePlan& p = m->ad.plan;
+    const uint32_t W = m->ad.W, H = m->ad.H;
+    bool in_group = false;
+    std::vector<PlanStep> group;   // logical transport: the group's sends / receives
+    auto body = [&]() -> int {
+        size_t i = 0;
+        std::vector<PlanStep> renders;   // the plan's leading steps: every part's passes, interleaved
+        for (; i < p.steps.size() && p.steps[i].op == OP_RENDER_ADAPTIVE; i++) renders.push_back(p.steps[i]);
+        if (int rc = render_adaptive_parts(m, renders, rci, opt, ad, acc, out, sample_count)) return rc;
+        for (; i < p.steps.size(); i++) {
+            const PlanStep& s = p.steps[i];
+            AdaptivePart& q = m->ad.parts[s.part];
+            const uint32_t nr = uint32_t(q.rows.size());
+            switch (s.op) {
+                case OP_GROUP_START:
+                    if (m->self_rccl) {
+                        if (int rc = self_group_fence(m, true)) return rc;
+                    }
+                    if (!m->logical || m->self_rccl) RT_NCCL(ncclGroupStart());
+                    group.clear();
+                    in_group = true;
+                    break;
+                case OP_GROUP_END:
+                    in_group = false;
+                    if (m->logical && !m->self_rccl) {
+                        if (int rc = adaptive_logical_transfers(m, group)) return rc;
+                    } else {
+                        RT_NCCL(ncclGroupEnd());
+                        if (m->self_rccl) {
+                            if (int rc = self_group_fence(m, false)) return rc;
+                        }
+                    }
+                    break;
+                case OP_SEND:
+                case OP_RECV:
+                case OP_SEND_COUNTS:
+                case OP_RECV_COUNTS: {
+                    if (m->logical && !m->self_rccl) {
+                        group.push_back(s);
+                        break;
+                    }
+                    // (self_rccl: rank 0 to itself on stream[0], the k-th send with the k-th receive)
+                    const uint32_t rank_dev = m->self_rccl ? 0u : s.dev;
+                    const int peer = m->self_rccl ? 0 : int(s.peer);
+                    const bool counts = s.op == OP_SEND_COUNTS || s.op == OP_RECV_COUNTS;
+                    const bool send = s.op == OP_SEND || s.op == OP_SEND_COUNTS;
+                    // a send reads the part's band / its context's tile table, a receive fills device 0's stages
+                    void* buf = counts ? (send ? const_cast<uint32_t*>(rt::adaptive_tile_counts(ctx_of(m, q.dev)))
+                                               : q.stage_counts)
+                                       : (send ? static_cast<void*>(q.acc) : static_cast<void*>(q.stage_acc));
+                    const ncclDataType_t ty = counts ? ncclUint32 : ncclFloat32;
+                    DeviceGuard g(phys_of(m, rank_dev));
+                    const ncclResult_t e = send ? ncclSend(buf, s.count, ty, peer, m->comm[rank_dev], m->stream[rank_dev])
+                                                : ncclRecv(buf, s.count, ty, peer, m->comm[rank_dev], m->stream[rank_dev]);
+                    if (e != ncclSuccess) return fail(RT_ERR_DEVICE, std::string("RCCL: ") + ncclGetErrorString(e));
+                    break;
+                }
+                case OP_STORE_TILES: {
+                    const float* src = q.dev == 0 ? q.acc : q.stage_acc;
+                    const uint32_t* counts = q.dev == 0 ? rt::adaptive_tile_counts(ctx_of(m, 0)) : q.stage_counts;
+                    if (int rc = rt::adaptive_store_tiles(phys_of(m, 0), src, nr, W, counts, q.rows_root, H, acc, out,
+                                                          sample_count, m->stream[0]))
+                        return rc;
+                    break;
+                }
+                default:
+                    return fail(RT_ERR_INVALID_ARGUMENT, "bad plan step");
+            }
+        }
+        return RT_OK;
+    };
+    const int rc = body();
+    if (in_group && (!m->logical || m->self_rccl)) (void)ncclGroupEnd();   // a failure inside a group still closes it
+    return rc;
+}
+
 int copy_plan(std::vector<uint32_t>&& v, uint32_t* out, uint64_t capacity, uint64_t* count) {
     *count = v.size();
     if (!out) return RT_OK;   // size query
@@ -552,6 +830,7 @@ int rt_debug_multi_create_logical_rccl(uint32_t n_devices, rt_multi** out) {
 
 int rt_multi_destroy(rt_multi* m) {
     if (!m) return RT_OK;
+    if (!m->phys.empty()) free_adaptive(m);
     if (!m->phys.empty()) free_launches(m);
     for (uint32_t d = 0; d < m->n && d < m->phys.size(); d++) {
         DeviceGuard g(phys_of(m, d));
@@ -626,6 +905,69 @@ int rt_multi_render(rt_multi* m, const RenderCallInfo* rci, const rt_options* op
     DeviceGuard g0(phys_of(m, 0));
     RT_HIP(hipEventRecord(m->ev_out, m->stream[0]));   // the caller's later work waits for it
     RT_HIP(hipStreamWaitEvent(st, m->ev_out, 0));
+    return RT_OK;
+}
+
+int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, const rt_adaptive* ad,
+                             float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info, void* stream) {
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!m || !rci) return fail(RT_ERR_INVALID_ARGUMENT, "m or rci is NULL");
+    if (!m->scene_set) return fail(RT_ERR_NO_SCENE, "rt_multi_render_adaptive before rt_multi_set_scene");
+    const uint32_t W = rci->image_size.x, H = rci->image_size.y;
+    if (W == 0 || H == 0) return fail(RT_ERR_INVALID_ARGUMENT, "image_size is zero");
+    if (!accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "accum or out is NULL");
+    {   // what needs no context is refused before anything is set up
+        rt_options o;
+        std::memset(&o, 0, sizeof(o));
+        if (opt) o = *opt;
+        if (int rc = rt::adaptive_check_values(rci, o, ad, "rt_multi_render_adaptive")) return rc;
+    }
+    try {
+        // the contexts and the scene as a first plain frame of this size sets them up; no balancer
+        // step, no record: adaptive frames are not re-dealt and leave the strip frames' history alone
+        if (int rc = set_partition(m, "strips", W, H, strip_parts(m->n, H))) return rc;
+        if (int rc = set_adaptive_partition(m, W, H)) {
+            const std::string msg = rt::g_last_error;
+            free_adaptive(m);
+            rt::g_last_error = msg;
+            return rc;
+        }
+        m->ad.info.assign(m->n, rt_adaptive_info{});
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_OUT_OF_MEMORY, e.what());
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    {   // the frame starts after the caller's earlier work on `stream` (device 0)
+        DeviceGuard g0(phys_of(m, 0));
+        RT_HIP(hipEventRecord(m->ev_in, st));
+        for (uint32_t d = 0; d < m->n; d++) RT_HIP(hipStreamWaitEvent(m->stream[d], m->ev_in, 0));
+    }
+    int rc;
+    try {
+        rc = run_adaptive_plan(m, rci, opt, ad, accum, out, sample_count);
+    } catch (const std::exception& e) {
+        rc = fail(RT_ERR_OUT_OF_MEMORY, e.what());
+    }
+    if (rc != RT_OK) return rc;
+    if (info) {   // the frame's totals: the one-device frame's numbers
+        for (const rt_adaptive_info& d : m->ad.info) {
+            info->passes = std::max(info->passes, d.passes);
+            info->tiles += d.tiles;
+            info->tiles_capped += d.tiles_capped;
+            info->samples += d.samples;
+        }
+    }
+    DeviceGuard g0(phys_of(m, 0));
+    RT_HIP(hipEventRecord(m->ev_out, m->stream[0]));   // the caller's later work waits for it
+    RT_HIP(hipStreamWaitEvent(st, m->ev_out, 0));
+    return RT_OK;
+}
+
+int rt_multi_adaptive_device_info(const rt_multi* m, uint32_t device, rt_adaptive_info* out) {
+    if (!m || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (device >= m->n) return fail(RT_ERR_INVALID_ARGUMENT, "device out of range");
+    std::memset(out, 0, sizeof(*out));
+    if (device < m->ad.info.size()) *out = m->ad.info[device];
     return RT_OK;
 }
 
@@ -720,6 +1062,36 @@ int rt_partition_strips(uint32_t n_devices, uint32_t height, uint32_t* rows, uin
         return fail(RT_ERR_OUT_OF_MEMORY, e.what());
     }
     return RT_OK;
+}
+
+int rt_partition_tile_rows(uint32_t n_devices, uint32_t height, uint32_t* rows, uint32_t* counts) {
+    if (n_devices == 0 || !rows || !counts) return fail(RT_ERR_INVALID_ARGUMENT, "zero devices or NULL output");
+    try {
+        const Parts parts = tile_row_parts(n_devices, height);
+        uint64_t at = 0;
+        for (uint32_t d = 0; d < n_devices; d++) counts[d] = 0;   // a device beyond the tile rows has no part
+        for (const auto& pr : parts) {
+            counts[pr.first] = uint32_t(pr.second.size());
+            std::memcpy(rows + at, pr.second.data(), pr.second.size() * 4);
+            at += pr.second.size();
+        }
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_OUT_OF_MEMORY, e.what());
+    }
+    return RT_OK;
+}
+
+int rt_debug_multi_plan_adaptive(uint32_t n_devices, uint32_t width, uint32_t height, uint32_t* out,
+                                 uint64_t capacity, uint64_t* count) {
+    if (!count) return fail(RT_ERR_INVALID_ARGUMENT, "count is NULL");
+    *count = 0;
+    if (n_devices == 0 || width == 0 || height == 0) return fail(RT_ERR_INVALID_ARGUMENT, "zero size");
+    try {
+        return copy_plan(serialize(make_adaptive_plan(width, height, tile_row_parts(n_devices, height))), out, capacity,
+                         count);
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_OUT_OF_MEMORY, e.what());
+    }
 }
 
 int rt_partition_rebalance(uint32_t n_devices, uint32_t height, uint32_t* rows, uint32_t* counts, double* row_cost,

@@ -23,6 +23,15 @@ Parts strip_parts(uint32_t n, uint32_t H) {
     return parts;
 }
 
+Parts tile_row_parts(uint32_t n, uint32_t H) {
+    const uint32_t T = H / kStrip + (H % kStrip ? 1u : 0u);
+    if (n == 0) return Parts{};
+    Parts parts(std::min(n, T));
+    for (uint32_t d = 0; d < parts.size(); d++) parts[d].first = d;
+    for (uint32_t y = 0; y < H; y++) parts[(y / kStrip) % n].second.push_back(y);
+    return parts;
+}
+
 Parts band_parts(uint32_t n, uint32_t H, const uint32_t* start, uint32_t n_bands) {
     Parts parts(n_bands);
     for (uint32_t i = 0; i < n_bands; i++) {
@@ -106,6 +115,49 @@ FramePlan make_plan(uint32_t W, uint32_t H, Parts&& parts, bool accumulate) {
     for (uint32_t i = 0; i < np; i++)
         if (live(i)) add(OP_STORE_ROWS, 0, 0, i, 0, floats(i));
     add(OP_RESOLVE, 0, 0, 0, 0, uint64_t(W) * H);
+    return p;
+}
+
+FramePlan make_adaptive_plan(uint32_t W, uint32_t H, Parts&& parts) {
+    FramePlan p;
+    for (auto& pr : parts) {
+        PlanPart q;
+        q.dev = pr.first;
+        q.rows = std::move(pr.second);
+        q.whole = q.dev == 0 && q.rows.size() == H;
+        for (uint32_t y = 0; q.whole && y < H; y++) q.whole = q.rows[y] == y;
+        p.parts.push_back(std::move(q));
+    }
+    const uint32_t np = uint32_t(p.parts.size());
+    auto live = [&](uint32_t i) { return !p.parts[i].rows.empty(); };
+    auto floats = [&](uint32_t i) { return uint64_t(p.parts[i].rows.size()) * W * 4u; };
+    auto words = [&](uint32_t i) {
+        return uint64_t((W + kStrip - 1) / kStrip) * ((p.parts[i].rows.size() + kStrip - 1) / kStrip);
+    };
+    auto add = [&](uint32_t op, uint32_t dev, uint32_t peer, uint32_t part, uint32_t flags, uint64_t count) {
+        p.steps.push_back(PlanStep{op, dev, peer, part, flags, count});
+    };
+    bool whole = false, remote = false;
+    for (uint32_t i = 0; i < np; i++) {
+        whole |= live(i) && p.parts[i].whole;
+        remote |= live(i) && p.parts[i].dev != 0;
+    }
+    for (uint32_t i = 0; i < np; i++)
+        if (live(i)) add(OP_RENDER_ADAPTIVE, p.parts[i].dev, p.parts[i].dev, i, p.parts[i].whole ? kDirect : 0u, 0);
+    if (whole) return p;
+    if (remote) {
+        add(OP_GROUP_START, 0, 0, 0, 0, 0);
+        for (uint32_t i = 0; i < np; i++) {
+            if (!live(i) || p.parts[i].dev == 0) continue;
+            add(OP_SEND, p.parts[i].dev, 0, i, 0, floats(i));
+            add(OP_RECV, 0, p.parts[i].dev, i, 0, floats(i));
+            add(OP_SEND_COUNTS, p.parts[i].dev, 0, i, 0, words(i));
+            add(OP_RECV_COUNTS, 0, p.parts[i].dev, i, 0, words(i));
+        }
+        add(OP_GROUP_END, 0, 0, 0, 0, 0);
+    }
+    for (uint32_t i = 0; i < np; i++)
+        if (live(i)) add(OP_STORE_TILES, 0, 0, i, 0, floats(i));
     return p;
 }
 

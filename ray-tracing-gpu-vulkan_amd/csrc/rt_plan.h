@@ -37,6 +37,14 @@ Parts band_parts(uint32_t n, uint32_t H, const uint32_t* start, uint32_t n_bands
 // Empty unless every row of [0, H) appears exactly once.
 Parts row_parts(uint32_t n, uint32_t H, const uint32_t* rows, const uint32_t* counts);
 
+// The partition of adaptive frames (rt_multi_render_adaptive): whole 8-row tile rows, because the
+// stop criterion is per 8x8 tile. Tile row k = global rows [8k, min(8k + 8, H)) goes to device
+// k % n; each device's rows ascend, and the ragged last tile row is globally last, so it is last in
+// its band: band tile row j of a part is exactly one global tile row, every band tile the same
+// pixel set as in the one-device frame. min(n, ceil(H / 8)) parts: a device without a tile row has
+// none. Static: adaptive frames are never re-dealt (a row's cost depends on where its tiles stop).
+Parts tile_row_parts(uint32_t n, uint32_t H);
+
 // ---- the frame plan --------------------------------------------------------------------
 // Buffers a step names: the caller's accumulator / rgba8 image on device 0 (W x H), each part's
 // band on its device (rows x W), and each remote part's stage on device 0 (rows x W float4).
@@ -50,6 +58,13 @@ enum PlanOp : uint32_t {
     OP_RENDER = 6,      // dev renders the part; flags bit 0: straight into the caller's buffers
     OP_STORE_ROWS = 7,  // device 0: the part's band (device 0) or stage -> its rows of the accumulator
     OP_RESOLVE = 8,     // device 0: rgba8 of the whole accumulator (`count` texels)
+    // adaptive frames (make_adaptive_plan); numbered above the plain frames' ops
+    OP_RENDER_ADAPTIVE = 9,   // dev renders the part to the noise level, pass by pass, interleaved with
+                              // the other parts' passes; flags bit 0: straight into the caller's buffers
+    OP_SEND_COUNTS = 10,      // dev -> peer: the part's per-tile sample counts, `count` 32-bit words
+    OP_RECV_COUNTS = 11,      // dev <- peer: into the part's count stage on device 0
+    OP_STORE_TILES = 12,      // device 0: the part's band (device 0) or stage + its count table -> its rows
+                              // of the accumulator, the rgba8 image and the count map (`count` floats)
 };
 constexpr uint32_t kDirect = 1u;
 
@@ -69,6 +84,12 @@ struct FramePlan {
 
 // The steps of one frame over `parts` (W x H), with or without accumulation (rt_multi.cpp).
 FramePlan make_plan(uint32_t W, uint32_t H, Parts&& parts, bool accumulate);
+
+// The steps of one adaptive frame over `parts` (tile_row_parts): every part renders; one group
+// brings each remote part's accumulator band and its count table (ceil(W / 8) * ceil(rows / 8)
+// words) to device 0; one fused store per part writes accumulator, rgba8 and counts in place (no
+// whole-image resolve). A `whole` part renders into the caller's buffers and needs nothing else.
+FramePlan make_adaptive_plan(uint32_t W, uint32_t H, Parts&& parts);
 
 // Flat form (rt_debug_multi_plan): {n_parts, n_steps}, per part {dev, whole, n_rows, rows...},
 // per step {op, dev, peer, part, flags, count low, count high}.

@@ -28,6 +28,7 @@ __all__ = [
     "make_options", "Renderer", "MultiRenderer", "render", "ray_trace", "store_ppm", "spheres_to_numpy",
     "load_library", "HASH", "STREAM", "multi_plan", "launch_inputs", "launch_plan", "row_weights", "struct_dict", "partition_strips", "partition_rebalance",
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
+    "partition_tile_rows", "multi_plan_adaptive",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -436,6 +437,44 @@ class MultiRenderer:
                                         ctypes.byref(options) if options is not None else None,
                                         accum.data_ptr(), out.data_ptr(), _stream_ptr(stream, 0)))
 
+    def render_adaptive(self, rci: RenderCallInfo, accum, out, sample_count=None,
+                        options: Optional[Options] = None, adaptive: Optional[Adaptive] = None,
+                        stream=None) -> AdaptiveInfo:
+        """One adaptive frame over the devices (rt_multi_render_adaptive) into device-0 tensors accum
+        (float32 [H, W, 4]), out (uint8 [H, W, 4]) and the optional sample_count (4-byte integer
+        [H, W]); `adaptive` from make_adaptive(), rci.samplesPerRenderCall the cap, options with
+        rng_mode HASH. Equals Renderer.render_adaptive on the whole image bit for bit. Blocks the
+        host on the per-pass readbacks only; the outputs are valid once `stream` completes. Returns
+        the frame's totals."""
+        if adaptive is None:
+            raise ValueError("adaptive is required (make_adaptive)")
+        W, H = rci.image_size.x, rci.image_size.y
+        _check_dev_tensor(accum, "torch.float32", (H, W, 4))
+        _check_dev_tensor(out, "torch.uint8", (H, W, 4))
+        if accum.device.index != 0 or out.device.index != 0:
+            raise ValueError("MultiRenderer.render_adaptive gathers to device 0: accum and out must live on cuda:0")
+        count_ptr = None
+        if sample_count is not None:
+            if not sample_count.is_cuda or sample_count.element_size() != 4 or sample_count.is_floating_point() \
+                    or not sample_count.is_contiguous() or tuple(sample_count.shape) != (H, W):
+                raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [H, W]")
+            if sample_count.device.index != 0:
+                raise ValueError("MultiRenderer.render_adaptive: sample_count must live on cuda:0")
+            count_ptr = sample_count.data_ptr()
+        info = AdaptiveInfo()
+        check(self._lib.rt_multi_render_adaptive(self._m, ctypes.byref(rci),
+                                                 ctypes.byref(options) if options is not None else None,
+                                                 ctypes.byref(adaptive), accum.data_ptr(), out.data_ptr(), count_ptr,
+                                                 ctypes.byref(info), _stream_ptr(stream, 0)))
+        return info
+
+    def adaptive_device_info(self, device: int) -> AdaptiveInfo:
+        """The last adaptive frame's numbers of one device (rt_multi_adaptive_device_info): the
+        imbalance of the static tile-row deal; zeros for a device that rendered nothing."""
+        info = AdaptiveInfo()
+        check(self._lib.rt_multi_adaptive_device_info(self._m, device, ctypes.byref(info)))
+        return info
+
     def info(self) -> dict:
         """{devices, rccl_ranks (ncclCommCount of the communicator), strip_rows, launches of the
         last frame} (rt_multi_info)."""
@@ -511,6 +550,16 @@ def partition_strips(n_devices: int, height: int) -> list:
     rows = np.zeros(max(1, height), np.uint32)
     check(load_library().rt_partition_strips(n_devices, height, rows.ctypes.data, counts.ctypes.data))
     return _split(rows, counts)
+
+
+def partition_tile_rows(n_devices: int, height: int) -> list:
+    """The static partition of adaptive multi-device frames (rt_partition_tile_rows): whole 8-row
+    tile rows dealt round robin, one uint32 array of global rows per device (empty beyond the tile
+    rows), band order."""
+    counts = np.zeros(max(1, n_devices), np.uint32)
+    rows = np.zeros(max(1, height), np.uint32)
+    check(load_library().rt_partition_tile_rows(n_devices, height, rows.ctypes.data, counts.ctypes.data))
+    return _split(rows, counts[:n_devices])
 
 
 def partition_rebalance(parts: Sequence, cost: np.ndarray, measured: Optional[Sequence] = None,
@@ -603,7 +652,8 @@ def struct_dict(s: ctypes.Structure) -> dict:
 
 
 PLAN_OPS = {1: "load_rows", 2: "group_start", 3: "send", 4: "recv", 5: "group_end", 6: "render",
-            7: "store_rows", 8: "resolve"}
+            7: "store_rows", 8: "resolve", 9: "render_adaptive", 10: "send_counts", 11: "recv_counts",
+            12: "store_tiles"}
 
 
 def multi_plan(n_devices: int, width: int, height: int, band_starts: Optional[Sequence[int]] = None,
@@ -626,6 +676,20 @@ def multi_plan(n_devices: int, width: int, height: int, band_starts: Optional[Se
         nb = 0 if band_starts is None else len(band_starts)
         call = lambda out, cap: lib.rt_debug_multi_plan(n_devices, width, height, bs, nb, int(accumulate),  # noqa: E731
                                                          out, cap, ctypes.byref(n))
+    return _read_plan(call, n)
+
+
+def multi_plan_adaptive(n_devices: int, width: int, height: int) -> dict:
+    """The plan of an adaptive frame (rt_debug_multi_plan_adaptive; host only): multi_plan's form
+    over partition_tile_rows' parts, with the ops render_adaptive, send_counts / recv_counts and
+    store_tiles."""
+    lib = load_library()
+    n = ctypes.c_uint64(0)
+    return _read_plan(lambda out, cap: lib.rt_debug_multi_plan_adaptive(n_devices, width, height, out, cap,
+                                                                       ctypes.byref(n)), n)
+
+
+def _read_plan(call, n) -> dict:
     check(call(None, 0))
     buf = np.zeros(n.value, np.uint32)
     check(call(buf.ctypes.data, n.value))

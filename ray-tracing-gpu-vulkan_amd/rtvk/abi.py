@@ -175,12 +175,16 @@ EXPORTS = {
     "rt_multi_device_count": (_I, [_P, ctypes.POINTER(_U32)]),
     "rt_multi_set_scene": (_I, [_P, _P, _U32]),
     "rt_multi_render": (_I, [_P, ctypes.POINTER(RenderCallInfo), ctypes.POINTER(Options), _P, _P, _P]),
+    "rt_multi_render_adaptive": (_I, [_P, ctypes.POINTER(RenderCallInfo), ctypes.POINTER(Options),
+                                      ctypes.POINTER(Adaptive), _P, _P, _P, ctypes.POINTER(AdaptiveInfo), _P]),
+    "rt_multi_adaptive_device_info": (_I, [_P, _U32, ctypes.POINTER(AdaptiveInfo)]),
     "rt_multi_stats": (_I, [_P, ctypes.POINTER(Stats)]),
     "rt_multi_info": (_I, [_P, _P]),
     "rt_multi_kernel_times": (_I, [_P, _P, _U32, ctypes.POINTER(_U32)]),
     "rt_multi_kernel_times_frames": (_I, [_P, _U32, _P, _U32, ctypes.POINTER(_U32)]),
     "rt_multi_partition": (_I, [_P, _P, _P, _U32]),
     "rt_partition_strips": (_I, [_U32, _U32, _P, _P]),
+    "rt_partition_tile_rows": (_I, [_U32, _U32, _P, _P]),
     "rt_partition_rebalance": (_I, [_U32, _U32, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.POINTER(_U32),
                                     ctypes.POINTER(ctypes.c_double)]),
     "rt_render": (_I, [_P, _U32, _P, _U32, _P, _P, ctypes.POINTER(Options), ctypes.POINTER(Stats)]),
@@ -208,6 +212,7 @@ EXPORTS = {
                                  ctypes.POINTER(ctypes.c_uint64)]),
     "rt_debug_multi_plan_rows": (_I, [_U32, _U32, _U32, _P, _P, _U32, _P, ctypes.c_uint64,
                                       ctypes.POINTER(ctypes.c_uint64)]),
+    "rt_debug_multi_plan_adaptive": (_I, [_U32, _U32, _U32, _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_debug_multi_create_logical": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_debug_multi_create_logical_rccl": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_debug_multi_tune": (_I, [_P, ctypes.c_char_p, ctypes.c_double]),
