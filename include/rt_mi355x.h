@@ -234,6 +234,72 @@ int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const 
  * E, S < 2^56, n <= 2^19, 1 <= m <= 64 (RT_ERR_INVALID_ARGUMENT otherwise). */
 int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16,
                                int* converged);
+/*
+ * Sample-map frames: "render this band with n[t] samples on 8x8 tile t". A sample
+ * map of a band of W x H texels is one uint32 count per tile, row-major with ceil(W/8) tiles per
+ * tile row (the layout of the adaptive tile table), each count in [0, 2^19], odd counts allowed.
+ * Every in-band pixel of tile t holds, bit for bit, what rt_render_device gives at
+ * samplesPerRenderCall = n[t] with the same options (RT_RNG_SAMPLE_HASH, accumulate 0): accum = the
+ * float sum with w = 1, rgba8 = unorm8(sqrt(sum / float(n))), the optional per-texel count = n[t].
+ * A tile with n = 0 is not traced: accum (0, 0, 0, 1), rgba8 (0, 0, 0, 255), the 0-sample frame.
+ * Plan: with L_0 < ... < L_{J-1} the distinct non-zero counts (L_{-1} = 0, J <=
+ * RT_SAMPLE_MAP_MAX_LEVELS, the launches rt_launch_ms keeps), the tiles sorted by (count descending,
+ * tile index ascending) and c_j = #{t : n[t] >= L_j}, launch j renders samples [L_{j-1}, L_j) on the
+ * first c_j tiles of that order: nested prefixes of one list, so every launch size is known before
+ * the frame starts and the whole frame is queued without a host wait: J trace launches into one set
+ * of fixed-point planes, then one resolve with the map as per-tile divisors.
+ *
+ * A map belongs to the context it was created on and must be destroyed before it. Setting it is the
+ * one synchronous step: the call waits for the queued frames that read the map, copies the table to
+ * the host behind the work queued on `stream`, plans it there (rt_sample_map_plan) and uploads the
+ * order and the quantised table. `quantum` (0 or 1: none) rounds every non-zero count up to a
+ * multiple of itself first: fewer launches for more samples. A count above 2^19 (before or after the
+ * quantum; the message names the first such tile) or more than 64 levels (the message suggests a
+ * quantum) is RT_ERR_INVALID_ARGUMENT and the map keeps what it held. info: optional.
+ */
+#define RT_SAMPLE_MAP_MAX_LEVELS 64u
+typedef struct rt_sample_map rt_sample_map;
+typedef struct rt_sample_map_info {
+    uint32_t tiles, levels;        /* tiles of the band; J                                        */
+    uint32_t min_count, max_count; /* smallest non-zero and largest count after quantum (0: none) */
+    uint64_t samples;              /* sum over tiles of n x in-band pixels                        */
+    uint64_t tile_launches;        /* sum of c_j                                                  */
+} rt_sample_map_info;
+int rt_sample_map_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_sample_map** out);
+int rt_sample_map_destroy(rt_sample_map* map);
+/* d_tile_counts: DEVICE array of ceil(W/8) * ceil(H/8) words, written by earlier work on `stream`. */
+int rt_sample_map_set_device(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t quantum,
+                             void* stream, rt_sample_map_info* info);
+/* The count table of the context's last completed adaptive frame (rt_render_adaptive_device; its
+ * band size must be the map's, RT_ERR_INVALID_ARGUMENT otherwise or without one). */
+int rt_sample_map_set_from_adaptive(rt_sample_map* map, uint32_t quantum, void* stream,
+                                    rt_sample_map_info* info);
+/* The info of the last successful set call (zeros but `tiles` before one). */
+int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out);
+/*
+ * One sample-map frame of a band, asynchronous on `stream`: arguments as rt_render_adaptive_device.
+ * The call contains no host wait, no event synchronisation and no blocking copy; a map may be
+ * rendered any number of times, on any stream of its context, between plain and adaptive calls.
+ *   rci->samplesPerRenderCall   the frame's cap, as in adaptive frames: >= the map's max_count,
+ *                  <= 2^19, and sample_base + samplesPerRenderCall must fit 32 bits.
+ *   opt            rng_mode must be RT_RNG_SAMPLE_HASH and accumulate 0.
+ * RT_ERR_INVALID_ARGUMENT before any work is queued (rt_last_error() names the field): rng_mode,
+ * accumulate, a band size other than the map's, the cap, a map never set, a map of another context,
+ * an adaptive frame open on ctx. RT_ERR_NO_SCENE before rt_set_scene.
+ * Each level's launch counts as one launch for rt_launch_ms; rt_get_stats reports the last launch.
+ * Map frames neither read nor update the tile order of rt_render_device launches, record no row
+ * weights and leave the count table of the last adaptive frame in place.
+ */
+int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
+                                uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
+                                const rt_sample_map* map, void* stream);
+/* The plan of a host table (host only, no device needed; what the two set calls compute): order and
+ * quantised hold n_tiles words, levels and level_tiles RT_SAMPLE_MAP_MAX_LEVELS; every output may be
+ * NULL. Refusals as the set calls'; nothing is written then. */
+int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum,
+                       uint32_t* order, uint32_t* levels, uint32_t* level_tiles, uint32_t* n_levels,
+                       uint32_t* quantised);
 /* Statistics of the last completed rt_render_device (synchronises ctx's last stream). */
 int rt_get_stats(rt_context* ctx, rt_stats* out);
 /* Trace-kernel duration (ms, HIP events on the launch stream) of ctx's launch `back` launches

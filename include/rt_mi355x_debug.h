@@ -97,6 +97,16 @@ int rt_debug_steals(rt_context* ctx, uint64_t* out);
  * first); *count = tiles (ceil(W/8) x ceil(H/8), row-major), 0 before the first launch. */
 int rt_debug_tile_cost(rt_context* ctx, uint32_t* out, uint64_t capacity, uint64_t* count);
 
+/* Diagnostic (tests): what the device holds of a sample map after its last set call, copied back:
+ * order and quantised (the map's tile count of words each, either may be NULL) from device memory,
+ * levels and level_tiles (RT_SAMPLE_MAP_MAX_LEVELS words each, either may be NULL) from the host
+ * plan the launches are sized by. Waits for the frames queued on the map. */
+int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* levels, uint32_t* level_tiles,
+                        uint32_t* quantised);
+/* The rt_sample_map_info a set call would report for a host table over a band (host only). */
+int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, uint32_t band_height,
+                             uint32_t quantum, rt_sample_map_info* out);
+
 /* Diagnostic (tests): copies one scene array of ctx to host memory. what: 0 geometry records,
  * 1 radii, 2 material records, 3 big-sphere ids, 4 LBVH nodes (padded), 5 LBVH nodes (unpadded),
  * 6 leaf geometry, 7 leaf ids, 8 info {u32 n_spheres, n_big, n_nodes, n_leaf_slots,

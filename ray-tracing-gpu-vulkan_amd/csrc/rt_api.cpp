@@ -13,6 +13,7 @@
 #include <cstring>
 #include <exception>
 #include <memory>
+#include <new>
 #include <random>
 #include <string>
 #include <utility>
@@ -28,6 +29,7 @@
 #include "rt_host.h"
 #include "rt_internal.h"
 #include "rt_launch.h"
+#include "rt_sample_map.h"
 
 namespace rt {
 hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
@@ -188,6 +190,9 @@ struct rt_context {
         rt::AdaptiveState* state = nullptr;     // device
         rt::AdaptiveState* host = nullptr;      // pinned copy, read after `ev` once per pass
         hipEvent_t ev = nullptr;
+        // the band of the last completed adaptive frame, whose count table the head of `tiles` still
+        // holds (0 x 0: none): rt_sample_map_set_from_adaptive reads it
+        uint32_t last_w = 0, last_h = 0;
         // The frame in flight, between rt::adaptive_begin and rt::adaptive_finish / adaptive_abort
         // (rt_host.h): the pass loop as a state machine, so that one host thread can interleave
         // the passes of several contexts (rt_multi_render_adaptive).
@@ -203,6 +208,21 @@ struct rt_context {
             const uint32_t* list = nullptr;     // their list (null: pass 0, every tile, row-major)
         } frame;
     } adaptive;
+};
+
+// A sample map: the plan of its last set call on the host (rt_sample_map.h) and,
+// on the device, what the launches and the resolve read. Rewritten only by a set call, which first
+// waits for `ev_read`, recorded behind every frame that renders the map.
+struct rt_sample_map {
+    rt_context* ctx = nullptr;
+    uint32_t band_w = 0, band_h = 0, n_tiles = 0;
+    uint32_t* table = nullptr;           // device: order[n_tiles], then the quantised counts[n_tiles]
+    uint32_t* stage = nullptr;           // pinned, 2 x n_tiles words: the set calls' copies
+    bool set = false;
+    rt::sample_map::Plan plan;
+    rt_sample_map_info info{};
+    hipEvent_t ev_read = nullptr;
+    mutable bool read_pending = false;   // ev_read has been recorded since the last set call
 };
 
 namespace {
@@ -1285,6 +1305,7 @@ int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStre
         }
         a.tiles = nullptr;
         a.cap_tiles = 0;
+        a.last_w = a.last_h = 0;
         void* p = nullptr;
         RT_HIP(hipMalloc(&p, n_tiles * 4u * sizeof(uint32_t)));
         a.tiles = static_cast<uint32_t*>(p);
@@ -1315,6 +1336,34 @@ AdaptiveBuffers adaptive_buffers(rt_context* ctx) {
     b.lists[0] = a.tiles + b.n_tiles;
     b.lists[1] = a.tiles + 2u * b.n_tiles;
     return b;
+}
+
+// The set calls of a sample map, the one synchronous step: waits for the frames
+// that read the map, brings the count table `d_counts` (written by earlier work on `st`) to the
+// host, plans it there and uploads the order and the quantised table. A refusal leaves the map as
+// it was.
+int sample_map_set(rt_sample_map* map, const uint32_t* d_counts, uint32_t quantum, hipStream_t st,
+                   rt_sample_map_info* info) {
+    const size_t n = map->n_tiles;
+    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+    map->read_pending = false;
+    RT_HIP(hipMemcpyAsync(map->stage, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RT_HIP(hipStreamSynchronize(st));
+    rt::sample_map::Plan plan;
+    rt_sample_map_info fresh{};
+    std::string err;
+    if (int rc = rt::sample_map::make_plan(map->stage, map->n_tiles, quantum, plan, &err)) return fail(rc, err);
+    if (int rc = rt::sample_map::totals(plan, map->band_w, map->band_h, &fresh, &err)) return fail(rc, err);
+    std::copy(plan.order.begin(), plan.order.end(), map->stage);
+    std::copy(plan.quantised.begin(), plan.quantised.end(), map->stage + n);
+    map->set = false;   // until the upload has landed
+    RT_HIP(hipMemcpyAsync(map->table, map->stage, 2u * n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    RT_HIP(hipStreamSynchronize(st));   // frames on any stream of the context may follow
+    map->plan = std::move(plan);
+    map->info = fresh;
+    map->set = true;
+    if (info) *info = fresh;
+    return RT_OK;
 }
 
 }  // namespace
@@ -1396,6 +1445,7 @@ int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* r
     f.list = nullptr;   // pass 0: every tile, row-major
     f.pending = false;
     f.open = true;      // from here on a failure leaves sums or state behind: adaptive_abort clears them
+    a.last_w = a.last_h = 0;   // the passes overwrite the last frame's count table
     if (hipError_t e = rt::launch_adaptive_init(a.state, st); e != hipSuccess)
         return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_init: ") + hipGetErrorString(e)));
     *open = true;
@@ -1501,6 +1551,8 @@ int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sampl
         info->samples = a.host->samples;
     }
     f.open = false;
+    a.last_w = P.band_w;
+    a.last_h = P.band_h;
     return render_issued(ctx, f.st);
 }
 
@@ -1668,6 +1720,195 @@ int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, u
     if (m == 0 || m > 64u) return fail(RT_ERR_INVALID_ARGUMENT, "m must be within 1 .. 64");
     *converged = rt::adaptive_tile_converged(E, S, n, m, thr_q16) ? 1 : 0;
     return RT_OK;
+}
+
+// ---- sample-map frames ------------------------------------------------------
+int rt_sample_map_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_sample_map** out) {
+    if (!ctx || !out) return fail(RT_ERR_INVALID_ARGUMENT, "ctx or out is NULL");
+    *out = nullptr;
+    if (band_width == 0 || band_height == 0 || band_width > 65535u || band_height > 65535u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be within 1 .. 65535");
+    const uint64_t n_tiles = uint64_t((band_width + 7u) / 8u) * ((band_height + 7u) / 8u);
+    if (n_tiles >= (1ull << 26)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
+    rt::DeviceGuard g(ctx->device);
+    std::unique_ptr<rt_sample_map> m(new (std::nothrow) rt_sample_map);
+    if (!m) return fail(RT_ERR_OUT_OF_MEMORY, "rt_sample_map_create: out of host memory");
+    m->ctx = ctx;
+    m->band_w = band_width;
+    m->band_h = band_height;
+    m->n_tiles = uint32_t(n_tiles);
+    m->info.tiles = m->n_tiles;
+    auto cleanup = [&](int rc) {
+        if (m->table) (void)hipFree(m->table);
+        if (m->stage) (void)hipHostFree(m->stage);
+        if (m->ev_read) (void)hipEventDestroy(m->ev_read);
+        return rc;
+    };
+    const size_t bytes = size_t(n_tiles) * 2u * sizeof(uint32_t);
+    if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->table), bytes); e != hipSuccess)
+        return cleanup(fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE,
+                            std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
+    if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&m->stage), bytes, hipHostMallocDefault); e != hipSuccess)
+        return cleanup(fail(RT_ERR_OUT_OF_MEMORY, std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
+    if (hipError_t e = hipEventCreateWithFlags(&m->ev_read, hipEventDisableTiming); e != hipSuccess)
+        return cleanup(fail(RT_ERR_DEVICE, std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
+    *out = m.release();
+    return RT_OK;
+}
+
+int rt_sample_map_destroy(rt_sample_map* map) {
+    if (!map) return RT_OK;
+    rt::DeviceGuard g(map->ctx->device);
+    if (map->read_pending) (void)hipEventSynchronize(map->ev_read);   // the frames that read it
+    (void)hipFree(map->table);
+    (void)hipHostFree(map->stage);
+    (void)hipEventDestroy(map->ev_read);
+    delete map;
+    return RT_OK;
+}
+
+int rt_sample_map_set_device(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t quantum, void* stream,
+                             rt_sample_map_info* info) {
+    if (!map || !d_tile_counts) return fail(RT_ERR_INVALID_ARGUMENT, "map or d_tile_counts is NULL");
+    rt::DeviceGuard g(map->ctx->device);
+    return sample_map_set(map, d_tile_counts, quantum, static_cast<hipStream_t>(stream), info);
+}
+
+int rt_sample_map_set_from_adaptive(rt_sample_map* map, uint32_t quantum, void* stream, rt_sample_map_info* info) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    rt_context* ctx = map->ctx;
+    const rt_context::Adaptive& a = ctx->adaptive;
+    if (a.frame.open)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_from_adaptive: an adaptive frame is open on this context");
+    if (a.last_w == 0 || !a.tiles)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_from_adaptive: the context has no completed adaptive frame");
+    if (a.last_w != map->band_w || a.last_h != map->band_h)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "rt_sample_map_set_from_adaptive: the last adaptive frame's band size " + std::to_string(a.last_w) +
+                        " x " + std::to_string(a.last_h) + " is not the map's " + std::to_string(map->band_w) + " x " +
+                        std::to_string(map->band_h));
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;   // behind the adaptive frame, whatever stream it ran on
+    return sample_map_set(map, a.tiles, quantum, st, info);
+}
+
+int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out) {
+    if (!map || !out) return fail(RT_ERR_INVALID_ARGUMENT, "map or out is NULL");
+    *out = map->info;
+    return RT_OK;
+}
+
+int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t* order,
+                       uint32_t* levels, uint32_t* level_tiles, uint32_t* n_levels, uint32_t* quantised) {
+    std::string err;
+    if (int rc = rt::sample_map::plan_arrays(tile_counts, n_tiles, quantum, order, levels, level_tiles, n_levels,
+                                             quantised, &err))
+        return fail(rc, err);
+    return RT_OK;
+}
+
+int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, uint32_t band_height, uint32_t quantum,
+                             rt_sample_map_info* out) {
+    if (band_width == 0 || band_height == 0 || band_width > 65535u || band_height > 65535u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be within 1 .. 65535");
+    const uint32_t n_tiles = ((band_width + 7u) / 8u) * ((band_height + 7u) / 8u);
+    rt::sample_map::Plan plan;
+    std::string err;
+    if (int rc = rt::sample_map::make_plan(tile_counts, n_tiles, quantum, plan, &err)) return fail(rc, err);
+    if (int rc = rt::sample_map::totals(plan, band_width, band_height, out, &err)) return fail(rc, err);
+    return RT_OK;
+}
+
+int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* levels, uint32_t* level_tiles,
+                        uint32_t* quantised) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map: the map was never set");
+    rt::DeviceGuard g(map->ctx->device);
+    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+    const size_t n = map->n_tiles;
+    if (order) RT_HIP(hipMemcpy(order, map->table, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (quantised) RT_HIP(hipMemcpy(quantised, map->table + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (levels) std::copy(map->plan.levels.begin(), map->plan.levels.end(), levels);
+    if (level_tiles) std::copy(map->plan.level_tiles.begin(), map->plan.level_tiles.end(), level_tiles);
+    return RT_OK;
+}
+
+// The whole frame is queued: one trace launch per level on the nested prefixes of the map's order,
+// then the resolve with the map as per-tile divisors. No host wait, no event synchronisation and no
+// blocking copy below (the buffers' first allocation and growth in adaptive_reserve aside).
+int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                                uint32_t band_height, float* accum, uint8_t* out, uint32_t* sample_count,
+                                const rt_options* opt, const rt_sample_map* map, void* stream) {
+    static const char* const who = "rt_render_sample_map_device";
+    rt_options o{};
+    bool empty = false;
+    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, &empty)) return rc;
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": map is NULL");
+    if (map->ctx != ctx) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map belongs to another context");
+    if (band_width != map->band_w || band_height != map->band_h)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": band size " + std::to_string(band_width) + " x " +
+                                                 std::to_string(band_height) + " is not the map's " +
+                                                 std::to_string(map->band_w) + " x " + std::to_string(map->band_h));
+    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map was never set");
+    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
+    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
+    const uint32_t cap = rci->samplesPerRenderCall;
+    if (cap < map->info.max_count)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
+                                                 " is below the map's max_count " + std::to_string(map->info.max_count));
+    if (uint64_t(o.sample_base) + cap > 0xffffffffull)
+        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + samplesPerRenderCall overflows 32 bits");
+    rt_context::Adaptive& a = ctx->adaptive;
+    if (a.frame.open)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is open on this context");
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;
+    TraceSetup S;
+    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
+    const uint64_t texels = uint64_t(band_width) * band_height;
+    if (int rc = adaptive_reserve(ctx, texels, S.n_tiles, st)) return rc;
+    rt::TraceParams& P = S.P;
+    // the adaptive planes, half A alone (B stays zero; the resolve leaves both zero), and for the walk
+    // kernels' unconditional tile-cost record a scratch table behind everything an adaptive frame
+    // uses of `tiles`: the last adaptive frame's count table stays in place
+    P.fixed = a.planes;
+    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * a.cap_tiles : nullptr;
+    P.tile_order = map->table;
+    P.accumulate = 0u;
+    P.head_tiles = 0u;
+    // after a failure between the first launch and the resolve the planes hold partial sums
+    auto abort = [&](int rc) {
+        const std::string msg = rt::g_last_error;
+        (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), st);
+        rt::g_last_error = msg;
+        if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
+        return rc;
+    };
+    uint32_t prev = 0;
+    for (size_t j = 0; j < map->plan.levels.size(); j++) {   // samples [L_{j-1}, L_j) on the first c_j tiles
+        const uint64_t c = map->plan.level_tiles[j];
+        P.spp = map->plan.levels[j] - prev;
+        P.sample_base = o.sample_base + prev;
+        // uniform chunks by rt_render_device's rule for the pixels of the prefix, as an adaptive
+        // pass does; no head / tail split (the order carries no cost order)
+        const char* err = "";
+        if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * c, c, true, false, &err)) return abort(fail(rc, err));
+        P.chunks = S.plan.chunks;
+        P.head_chunks = S.plan.head_chunks;
+        P.n_units = S.plan.n_units;
+        if (int rc = launch_units(ctx, S, st)) return abort(rc);
+        prev = map->plan.levels[j];
+    }
+    if (hipError_t e = rt::launch_adaptive_resolve(a.planes, a.planes + 3u * texels, texels, band_width, P.tiles_x,
+                                                   map->table + map->n_tiles, accum, out, sample_count, st);
+        e != hipSuccess)
+        return abort(fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
+    RT_HIP(hipEventRecord(map->ev_read, st));   // the next set call waits for this frame
+    map->read_pending = true;
+    return render_issued(ctx, st);
 }
 
 int rt_get_stats(rt_context* ctx, rt_stats* out) {

@@ -16,6 +16,11 @@
 //   --adaptive THRESHOLD[,MIN[,STEP]]: one adaptive frame (rt_render_adaptive_device) on one GPU
 //   in the counter-based stream: MIN samples everywhere (default 16), STEP more per pass (default
 //   MIN) on the 8x8 tiles noisier than THRESHOLD, at most --samples per pixel.
+//   --adaptive ... --frames <n> [--animate] [--replay R]: the frame loop on one GPU with adaptive
+//   frames: frame i is an adaptive frame when i % (R + 1) == 0 (R defaults to 0), else a sample-map
+//   frame (rt_render_sample_map_device) that replays the latest adaptive frame's per-tile counts
+//   without the pass loop, queued asynchronously; duration_per_frame adds the replays and the mean
+//   spp. --replay without --adaptive and --frames is refused.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -166,6 +171,92 @@ int run_adaptive(uint32_t samples, uint32_t width, uint32_t height, bool store, 
     return 0;
 }
 
+// The frame loop with adaptive frames, on device 0: frame i is an adaptive frame when
+// i % (replay + 1) == 0, else a sample-map frame replaying the latest adaptive frame's counts. One
+// stream, the scene rebuilt per frame as run_frames does; the replays are queued without a host wait.
+int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate, bool store,
+                        const rt_adaptive& ad, uint32_t replay) {
+    rt_context* ctx = nullptr;
+    rt_sample_map* map = nullptr;
+    hipStream_t stream = nullptr;
+    float* accum = nullptr;
+    uint8_t* rgba8 = nullptr;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_RT(rt_sample_map_create(ctx, width, height, &map));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    CLI_HIP(hipMalloc(&accum, size_t(width) * height * 16));
+    CLI_HIP(hipMalloc(&rgba8, size_t(width) * height * 4));
+    rt_options opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0;
+    uint64_t frame_index = 0, window_samples = 0;
+    uint32_t window_replays = 0;
+    bool map_stale = true;   // an adaptive frame has run since the map was set
+    rt_sample_map_info map_info;
+    std::memset(&map_info, 0, sizeof(map_info));
+    const auto t_start = std::chrono::steady_clock::now();
+    auto frame = [&]() -> int {
+        const float t = animate ? std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() : 0.0f;
+        CLI_RT(rt_generate_scene(t, 11, scene.data(), uint32_t(scene.size()), &cnt));
+        RenderCallInfo rci;
+        CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+        CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+        if (frame_index % (uint64_t(replay) + 1u) == 0) {
+            rt_adaptive_info info;
+            CLI_RT(rt_render_adaptive_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, &ad, &info,
+                                             stream));
+            window_samples += info.samples;
+            map_stale = true;
+        } else {
+            if (map_stale) CLI_RT(rt_sample_map_set_from_adaptive(map, 0, stream, &map_info));
+            map_stale = false;
+            CLI_RT(rt_render_sample_map_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, map, stream));
+            window_samples += map_info.samples;
+            ++window_replays;
+        }
+        ++frame_index;
+        return 0;
+    };
+    if (int rc = frame()) return rc;   // warm-up: the adaptive buffers exist
+    CLI_HIP(hipStreamSynchronize(stream));
+    frame_index = 0;
+    const double pixels = double(width) * height;
+    uint32_t done = 0;
+    while (done < frames) {
+        const auto b = std::chrono::steady_clock::now();
+        uint32_t k = 0;
+        window_samples = 0;
+        window_replays = 0;
+        for (;;) {
+            if (int rc = frame()) return rc;
+            ++k;
+            if (done + k >= frames) break;
+            if (std::chrono::steady_clock::now() - b > std::chrono::milliseconds(1000)) break;
+        }
+        CLI_HIP(hipStreamSynchronize(stream));
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+        done += k;
+        std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u replays, mean %.2f spp of at most "
+                    "%u, %.1f Msamples/s)\n",
+                    sec / k * 1e3, k, double(ad.threshold), window_replays, double(window_samples) / pixels / k, samples,
+                    double(window_samples) / sec / 1e6);
+    }
+    if (store) {   // the last frame
+        std::vector<uint8_t> img(size_t(width) * height * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_sample_map_destroy(map);
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    (void)hipFree(accum);
+    (void)hipFree(rgba8);
+    return 0;
+}
+
 // THRESHOLD[,MIN[,STEP]]
 bool parse_adaptive(const char* s, rt_adaptive& ad) {
     std::memset(&ad, 0, sizeof(ad));
@@ -189,7 +280,8 @@ bool parse_adaptive(const char* s, rt_adaptive& ad) {
 
 int main(int argc, const char** argv) {
     uint32_t samples = 10, width = 1920, height = 1080, gpu_count = 1, frames = 0, rng_mode = RT_RNG_PIXEL_STREAM;
-    bool rng_explicit = false;
+    uint32_t replay = 0;
+    bool rng_explicit = false, replay_given = false;
     bool store = false, animate = false, adaptive = false;
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
@@ -207,6 +299,8 @@ int main(int argc, const char** argv) {
             std::puts("--rng <stream|hash>               # Reference per-pixel LCG stream (default) or counter-based stream");
             std::puts("--adaptive <thr>[,<min>[,<step>]] # One GPU, hash stream: min spp everywhere, step more per pass on");
             std::puts("                                  # tiles noisier than thr, at most --samples per pixel");
+            std::puts("--replay <count>                  # With --adaptive and --frames: after each adaptive frame, count");
+            std::puts("                                  # frames replay its per-tile sample counts (no pass loop)");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -226,7 +320,8 @@ int main(int argc, const char** argv) {
             }
             rng_mode = std::strcmp(argv[++i], "hash") == 0 ? RT_RNG_SAMPLE_HASH : RT_RNG_PIXEL_STREAM;
             rng_explicit = true;
-        } else if (a == "--samples" || a == "--width" || a == "--height" || a == "--gpus" || a == "--frames") {
+        } else if (a == "--samples" || a == "--width" || a == "--height" || a == "--gpus" || a == "--frames" ||
+                   a == "--replay") {
             uint32_t v = 0;
             if (i + 1 >= argc || !parse_u32(argv[i + 1], v)) {
                 std::fprintf(stderr, "%s needs an unsigned integer value\n", a.c_str());
@@ -237,10 +332,15 @@ int main(int argc, const char** argv) {
             else if (a == "--width") width = v;
             else if (a == "--height") height = v;
             else if (a == "--frames") frames = v;
+            else if (a == "--replay") { replay = v; replay_given = true; }
             else gpu_count = v;
         } else {
             std::fprintf(stderr, "unknown argument: %s\n", argv[i]);
         }
+    }
+    if (replay_given && !(adaptive && frames > 0)) {
+        std::fprintf(stderr, "--replay needs --adaptive and --frames\n");
+        return 2;
     }
     if (adaptive) {   // refused before anything renders
         if (rng_explicit && rng_mode != RT_RNG_SAMPLE_HASH) {
@@ -251,16 +351,13 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--adaptive renders on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
-        if (frames > 0) {
-            std::fprintf(stderr, "--adaptive renders one frame: it cannot run with --frames\n");
-            return 2;
-        }
     }
     int n = 0;
     if (rt_device_count(&n) != RT_OK) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
+    if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay);
     if (adaptive) return run_adaptive(samples, width, height, store, ad);
     if (frames > 0) return run_frames(samples, width, height, gpu_count, frames, animate, store, rng_mode);
     // ray_trace() keeps the reference's signature; its stream is selected through RT_RNG. An

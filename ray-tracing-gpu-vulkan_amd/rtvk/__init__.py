@@ -13,6 +13,7 @@ torch tensors (memory + stream plumbing only).
 from __future__ import annotations
 
 import ctypes
+import weakref
 from dataclasses import dataclass
 from typing import Iterable, Optional, Sequence
 
@@ -28,7 +29,7 @@ __all__ = [
     "make_options", "Renderer", "MultiRenderer", "render", "ray_trace", "store_ppm", "spheres_to_numpy",
     "load_library", "HASH", "STREAM", "multi_plan", "launch_inputs", "launch_plan", "row_weights", "struct_dict", "partition_strips", "partition_rebalance",
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
-    "partition_tile_rows", "multi_plan_adaptive",
+    "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -124,8 +125,11 @@ class Renderer:
         check(self._lib.rt_context_create(device, ctypes.byref(self._ctx)))
         self.device = device
         self.sphere_count = 0
+        self._maps = weakref.WeakSet()
 
     def close(self) -> None:
+        for m in list(getattr(self, "_maps", ())):
+            m.close()
         if self._ctx:
             self._lib.rt_context_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
@@ -268,6 +272,39 @@ class Renderer:
                                                   _stream_ptr(stream, self.device)))
         return info
 
+    def sample_map(self, width: int, height: int) -> "SampleMap":
+        """A sample map of a band of width x height texels on this context (rt_sample_map_create):
+        one count per 8x8 tile. Close it before the renderer."""
+        m = SampleMap(self, width, height)
+        self._maps.add(m)   # closed with the renderer at the latest
+        return m
+
+    def render_sample_map(self, rci: RenderCallInfo, accum, out, smap: "SampleMap", sample_count=None, rows=None,
+                          options: Optional[Options] = None, stream=None) -> None:
+        """One band with smap's per-tile sample counts (rt_render_sample_map_device): every pixel of a
+        tile with count n holds what render_device gives at n samples; rci.samplesPerRenderCall is
+        the cap (>= the map's max_count), options with rng_mode HASH. Tensors as render_adaptive.
+        Asynchronous on `stream`: the whole frame is queued without a host wait."""
+        bh, bw = int(accum.shape[0]), int(accum.shape[1])
+        _check_dev_tensor(accum, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        rows_ptr = None
+        if rows is not None:
+            if rows.numel() != bh or not rows.is_cuda or rows.element_size() != 4 or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous 4-byte cuda tensor of band_h entries")
+            rows_ptr = rows.data_ptr()
+        count_ptr = None
+        if sample_count is not None:
+            if not sample_count.is_cuda or sample_count.element_size() != 4 or sample_count.is_floating_point() \
+                    or not sample_count.is_contiguous() or tuple(sample_count.shape) != (bh, bw):
+                raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            count_ptr = sample_count.data_ptr()
+        check(self._lib.rt_render_sample_map_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
+                                                    accum.data_ptr(), out.data_ptr(), count_ptr,
+                                                    ctypes.byref(options) if options is not None else None,
+                                                    smap._map if smap is not None else None,
+                                                    _stream_ptr(stream, self.device)))
+
     def stats(self) -> Stats:
         st = Stats()
         check(self._lib.rt_get_stats(self._ctx, ctypes.byref(st)))
@@ -380,6 +417,104 @@ class Renderer:
         got = ctypes.c_uint32(0)
         check(self._lib.rt_debug_kernel_times(self._ctx, buf, n, ctypes.byref(got)))
         return [float(buf[i]) for i in range(got.value)]
+
+
+class SampleMap:
+    """Per-tile sample counts of a band on one Renderer (rt_sample_map). Setting
+    the map is the one synchronous step; Renderer.render_sample_map then queues whole frames."""
+
+    def __init__(self, renderer: Renderer, width: int, height: int):
+        self._lib = renderer._lib
+        self._map = ctypes.c_void_p()
+        self.renderer = renderer
+        self.width, self.height = int(width), int(height)
+        self.tiles_x, self.tiles_y = (self.width + 7) // 8, (self.height + 7) // 8
+        check(self._lib.rt_sample_map_create(renderer._ctx, self.width, self.height, ctypes.byref(self._map)))
+
+    def close(self) -> None:
+        if self._map:
+            self._lib.rt_sample_map_destroy(self._map)
+            self._map = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set(self, tile_counts, quantum: int = 0, stream=None) -> abi.SampleMapInfo:
+        """tile_counts: contiguous 4-byte integer cuda tensor of tiles_y x tiles_x counts (row-major;
+        any shape with that many entries), written by earlier work on `stream`; quantum rounds every
+        non-zero count up to a multiple of itself (rt_sample_map_set_device)."""
+        n = self.tiles_x * self.tiles_y
+        if not tile_counts.is_cuda or tile_counts.element_size() != 4 or tile_counts.is_floating_point() \
+                or not tile_counts.is_contiguous() or tile_counts.numel() != n:
+            raise ValueError(f"tile_counts must be a contiguous 4-byte integer cuda tensor of {n} entries")
+        info = abi.SampleMapInfo()
+        check(self._lib.rt_sample_map_set_device(self._map, tile_counts.data_ptr(), quantum,
+                                                 _stream_ptr(stream, self.renderer.device), ctypes.byref(info)))
+        return info
+
+    def set_from_adaptive(self, quantum: int = 0, stream=None) -> abi.SampleMapInfo:
+        """The count table of the renderer's last completed adaptive frame of this band size
+        (rt_sample_map_set_from_adaptive)."""
+        info = abi.SampleMapInfo()
+        check(self._lib.rt_sample_map_set_from_adaptive(self._map, quantum, _stream_ptr(stream, self.renderer.device),
+                                                        ctypes.byref(info)))
+        return info
+
+    @property
+    def info(self) -> abi.SampleMapInfo:
+        info = abi.SampleMapInfo()
+        check(self._lib.rt_sample_map_get_info(self._map, ctypes.byref(info)))
+        return info
+
+    def debug_plan(self) -> dict:
+        """What the device holds after the last set call (rt_debug_sample_map), in sample_map_plan's form."""
+        n = self.tiles_x * self.tiles_y
+        order, quantised = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        levels = np.zeros(abi.SAMPLE_MAP_MAX_LEVELS, np.uint32)
+        level_tiles = np.zeros(abi.SAMPLE_MAP_MAX_LEVELS, np.uint32)
+        check(self._lib.rt_debug_sample_map(self._map, order.ctypes.data, levels.ctypes.data, level_tiles.ctypes.data,
+                                            quantised.ctypes.data))
+        j = self.info.levels
+        return {"order": order, "levels": levels[:j].copy(), "level_tiles": level_tiles[:j].copy(),
+                "quantised": quantised}
+
+
+def sample_map_plan(counts, quantum: int = 0) -> dict:
+    """The plan of a host table of per-tile sample counts (rt_sample_map_plan; host only, no GPU
+    needed): {order, levels, level_tiles, quantised} as uint32 arrays. Launch j of a sample-map frame
+    renders samples [levels[j-1], levels[j]) on the tiles order[:level_tiles[j]]. Raises RtError for
+    what the library refuses (a count above 2^19, more than 64 levels)."""
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.uint32)
+    n = len(c)
+    order, quantised = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    levels = np.zeros(abi.SAMPLE_MAP_MAX_LEVELS, np.uint32)
+    level_tiles = np.zeros(abi.SAMPLE_MAP_MAX_LEVELS, np.uint32)
+    j = ctypes.c_uint32(0)
+    check(load_library().rt_sample_map_plan(c.ctypes.data if n else None, n, quantum, order.ctypes.data if n else None,
+                                            levels.ctypes.data, level_tiles.ctypes.data, ctypes.byref(j),
+                                            quantised.ctypes.data if n else None))
+    return {"order": order, "levels": levels[:j.value].copy(), "level_tiles": level_tiles[:j.value].copy(),
+            "quantised": quantised}
+
+
+def sample_map_info(counts, width: int, height: int, quantum: int = 0) -> abi.SampleMapInfo:
+    """The SampleMapInfo a set call reports for the host table `counts` over a width x height band
+    (rt_debug_sample_map_info; host only)."""
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.uint32)
+    if len(c) != ((width + 7) // 8) * ((height + 7) // 8):
+        raise ValueError("one count per 8x8 tile of the band")
+    info = abi.SampleMapInfo()
+    check(load_library().rt_debug_sample_map_info(c.ctypes.data, width, height, quantum, ctypes.byref(info)))
+    return info
 
 
 class MultiRenderer:

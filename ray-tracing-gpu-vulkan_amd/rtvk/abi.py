@@ -100,6 +100,16 @@ class AdaptiveInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32), ("samples", ctypes.c_uint64)]
 
 
+SAMPLE_MAP_MAX_LEVELS = 64   # RT_SAMPLE_MAP_MAX_LEVELS
+SAMPLE_MAP_MAX_COUNT = 1 << 19
+
+
+class SampleMapInfo(ctypes.Structure):
+    """rt_sample_map_info (include/rt_mi355x.h)."""
+    _fields_ = [("tiles", ctypes.c_uint32), ("levels", ctypes.c_uint32), ("min_count", ctypes.c_uint32),
+                ("max_count", ctypes.c_uint32), ("samples", ctypes.c_uint64), ("tile_launches", ctypes.c_uint64)]
+
+
 TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
                "unit_min_samples", "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule", "refill_reserve",
                "isolate_tiles", "sah_knobs")
@@ -143,6 +153,7 @@ assert ctypes.sizeof(Scene) == 41024 and Scene.sphereAmount.offset == 40960
 assert ctypes.sizeof(RenderCallInfo) == 64 and RenderCallInfo.camera_dir.offset == 48
 assert ctypes.sizeof(Options) == 32
 assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and AdaptiveInfo.samples.offset == 16
+assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
 _P, _U32, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
@@ -164,6 +175,16 @@ EXPORTS = {
                                        ctypes.POINTER(Options), ctypes.POINTER(Adaptive),
                                        ctypes.POINTER(AdaptiveInfo), _P]),
     "rt_adaptive_tile_converged": (_I, [ctypes.c_uint64, ctypes.c_uint64, _U32, _U32, _U32, ctypes.POINTER(_I)]),
+    "rt_sample_map_create": (_I, [_P, _U32, _U32, ctypes.POINTER(_P)]),
+    "rt_sample_map_destroy": (_I, [_P]),
+    "rt_sample_map_set_device": (_I, [_P, _P, _U32, _P, ctypes.POINTER(SampleMapInfo)]),
+    "rt_sample_map_set_from_adaptive": (_I, [_P, _U32, _P, ctypes.POINTER(SampleMapInfo)]),
+    "rt_sample_map_get_info": (_I, [_P, ctypes.POINTER(SampleMapInfo)]),
+    "rt_render_sample_map_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
+                                         ctypes.POINTER(Options), _P, _P]),
+    "rt_sample_map_plan": (_I, [_P, _U32, _U32, _P, _P, _P, ctypes.POINTER(_U32), _P]),
+    "rt_debug_sample_map": (_I, [_P, _P, _P, _P, _P]),
+    "rt_debug_sample_map_info": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(SampleMapInfo)]),
     "rt_get_stats": (_I, [_P, ctypes.POINTER(Stats)]),
     "rt_launch_ms": (_I, [_P, _U32, ctypes.POINTER(ctypes.c_float)]),
     "rt_launch_row_weights": (_I, [_P, _U32, _P, _U32]),
