@@ -1281,35 +1281,63 @@ int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
     return RT_OK;
 }
 
-// Buffers of an adaptive frame of `texels` texels in `n_tiles` tiles. Growing frees the old ones
-// after the stream has drained (every earlier op of ctx is ordered before it).
+// One trace launch of `spp` samples from `sample_base` on the first `c` tiles of S.P.tile_order
+// (null: row-major), a half-pass of an adaptive frame or a level of a sample-map frame: uniform
+// chunks by rt_render_device's rule for the pixels of those tiles, no head / tail split (the list
+// carries no cost order).
+int launch_tile_prefix(rt_context* ctx, TraceSetup& S, uint32_t spp, uint32_t sample_base, uint64_t c, bool ordered,
+                       hipStream_t st) {
+    rt::TraceParams& P = S.P;
+    P.spp = spp;
+    P.sample_base = sample_base;
+    const char* err = "";
+    if (int rc = rt::launch::split_units(S.in, S.plan, spp, 64u * c, c, ordered, false, &err)) return fail(rc, err);
+    P.chunks = S.plan.chunks;
+    P.head_chunks = S.plan.head_chunks;
+    P.n_units = S.plan.n_units;
+    return launch_units(ctx, S, st);
+}
+
+// The recovery of a frame on the adaptive planes that failed with `rc` after its first launch: the
+// planes are zero between calls, whatever happened. Keeps the first error and its message.
+int abort_on_planes(rt_context* ctx, hipStream_t st, int rc) {
+    rt_context::Adaptive& a = ctx->adaptive;
+    const std::string msg = rt::g_last_error;
+    (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), st);
+    rt::g_last_error = msg;
+    if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
+    return rc;
+}
+
+// Grows a device buffer that work queued on `st` may still read to `count` units of `unit` bytes
+// (sum planes: zeroed on `st`). An old buffer is freed after the stream has drained (every earlier
+// op of ctx is ordered before it); the new buffer and its capacity are set after success only
+// (a failed growth leaves none).
+template <class T>
+int grow_on_stream(T*& buf, uint64_t& cap, uint64_t count, size_t unit, bool zero, hipStream_t st) {
+    if (buf) {
+        RT_HIP(hipStreamSynchronize(st));
+        RT_HIP(hipFree(buf));
+    }
+    buf = nullptr;
+    cap = 0;
+    void* p = nullptr;
+    RT_HIP(hipMalloc(&p, count * unit));
+    if (zero) RT_HIP(hipMemsetAsync(p, 0, count * unit, st));
+    buf = static_cast<T*>(p);
+    cap = count;
+    return RT_OK;
+}
+
+// Buffers of an adaptive frame of `texels` texels in `n_tiles` tiles.
 int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStream_t st) {
     rt_context::Adaptive& a = ctx->adaptive;
     if (a.cap < texels) {
-        if (a.planes) {
-            RT_HIP(hipStreamSynchronize(st));
-            RT_HIP(hipFree(a.planes));
-        }
-        a.planes = nullptr;
-        a.cap = 0;
-        void* p = nullptr;
-        RT_HIP(hipMalloc(&p, texels * 6u * sizeof(unsigned long long)));
-        RT_HIP(hipMemsetAsync(p, 0, texels * 6u * sizeof(unsigned long long), st));
-        a.planes = static_cast<unsigned long long*>(p);
-        a.cap = texels;
+        if (int rc = grow_on_stream(a.planes, a.cap, texels, 6u * sizeof(unsigned long long), true, st)) return rc;
     }
     if (a.cap_tiles < n_tiles) {
-        if (a.tiles) {
-            RT_HIP(hipStreamSynchronize(st));
-            RT_HIP(hipFree(a.tiles));
-        }
-        a.tiles = nullptr;
-        a.cap_tiles = 0;
-        a.last_w = a.last_h = 0;
-        void* p = nullptr;
-        RT_HIP(hipMalloc(&p, n_tiles * 4u * sizeof(uint32_t)));
-        a.tiles = static_cast<uint32_t*>(p);
-        a.cap_tiles = n_tiles;
+        a.last_w = a.last_h = 0;   // the last frame's count table goes with the old buffer
+        if (int rc = grow_on_stream(a.tiles, a.cap_tiles, n_tiles, 4u * sizeof(uint32_t), false, st)) return rc;
     }
     if (!a.state) RT_HIP(hipMalloc(reinterpret_cast<void**>(&a.state), sizeof(rt::AdaptiveState)));
     if (!a.host) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&a.host), sizeof(rt::AdaptiveState), hipHostMallocDefault));
@@ -1406,12 +1434,8 @@ int adaptive_abort(rt_context* ctx, int rc) {
     rt_context::Adaptive& a = ctx->adaptive;
     if (!a.frame.open) return rc;
     DeviceGuard g(ctx->device);
-    const std::string msg = rt::g_last_error;   // the half-buffers are zero between calls, whatever happened
-    (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), a.frame.st);
-    rt::g_last_error = msg;
     a.frame.open = a.frame.pending = false;
-    if (int rc2 = render_issued(ctx, a.frame.st)) return rc ? rc : rc2;
-    return rc;
+    return abort_on_planes(ctx, a.frame.st, rc);
 }
 
 int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
@@ -1465,19 +1489,11 @@ int adaptive_issue_pass(rt_context* ctx) {
     hipStream_t st = f.st;
     const uint32_t k = f.passes == 0 ? f.ad.min_spp : std::min(f.ad.step_spp, f.max_spp - f.done);
     for (uint32_t h = 0; h < 2; h++) {   // samples [done, done + k/2) into A, the next k/2 into B
-        P.spp = k / 2u;
-        P.sample_base = f.o.sample_base + f.done + h * (k / 2u);
         P.fixed = b.half[h];
         P.tile_order = f.list;
-        // uniform chunks by rt_render_device's rule for the pixels of the list; no head / tail
-        // split (the list carries no cost order)
-        const char* err = "";
-        if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * f.active, f.active, f.list != nullptr, false, &err))
-            return fail(rc, err);
-        P.chunks = S.plan.chunks;
-        P.head_chunks = S.plan.head_chunks;
-        P.n_units = S.plan.n_units;
-        if (int rc = launch_units(ctx, S, st)) return rc;
+        if (int rc = launch_tile_prefix(ctx, S, k / 2u, f.o.sample_base + f.done + h * (k / 2u), f.active,
+                                        f.list != nullptr, st))
+            return rc;
     }
     f.done += k;
     rt::AdaptiveErrorParams K;
@@ -1610,18 +1626,9 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
     const uint64_t texels = uint64_t(band_width) * band_height;
     if (mode == rt::MODE_HASH) {
         if (ctx->fixed_cap < texels) {
-            if (ctx->fixed) {
-                RT_HIP(hipStreamSynchronize(st));   // ordered after every earlier op of ctx
-                RT_HIP(hipFree(ctx->fixed));
-            }
-            ctx->fixed = nullptr;
-            ctx->fixed_cap = 0;
-            void* p = nullptr;
             constexpr size_t kPlanes = 3;   // (texel-major, one 32-B sector per texel: +22 % WRITE_SIZE)
-            RT_HIP(hipMalloc(&p, texels * kPlanes * sizeof(unsigned long long)));
-            RT_HIP(hipMemsetAsync(p, 0, texels * kPlanes * sizeof(unsigned long long), st));
-            ctx->fixed = static_cast<unsigned long long*>(p);
-            ctx->fixed_cap = texels;
+            if (int rc = grow_on_stream(ctx->fixed, ctx->fixed_cap, texels, kPlanes * sizeof(unsigned long long), true, st))
+                return rc;
         }
         P.fixed = ctx->fixed;
     }
@@ -1879,33 +1886,19 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
     P.tile_order = map->table;
     P.accumulate = 0u;
     P.head_tiles = 0u;
-    // after a failure between the first launch and the resolve the planes hold partial sums
-    auto abort = [&](int rc) {
-        const std::string msg = rt::g_last_error;
-        (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), st);
-        rt::g_last_error = msg;
-        if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
-        return rc;
-    };
+    // (after a failure between the first launch and the resolve the planes hold partial sums:
+    // abort_on_planes)
     uint32_t prev = 0;
     for (size_t j = 0; j < map->plan.levels.size(); j++) {   // samples [L_{j-1}, L_j) on the first c_j tiles
-        const uint64_t c = map->plan.level_tiles[j];
-        P.spp = map->plan.levels[j] - prev;
-        P.sample_base = o.sample_base + prev;
-        // uniform chunks by rt_render_device's rule for the pixels of the prefix, as an adaptive
-        // pass does; no head / tail split (the order carries no cost order)
-        const char* err = "";
-        if (int rc = rt::launch::split_units(S.in, S.plan, P.spp, 64u * c, c, true, false, &err)) return abort(fail(rc, err));
-        P.chunks = S.plan.chunks;
-        P.head_chunks = S.plan.head_chunks;
-        P.n_units = S.plan.n_units;
-        if (int rc = launch_units(ctx, S, st)) return abort(rc);
-        prev = map->plan.levels[j];
+        const uint32_t level = map->plan.levels[j];
+        if (int rc = launch_tile_prefix(ctx, S, level - prev, o.sample_base + prev, map->plan.level_tiles[j], true, st))
+            return abort_on_planes(ctx, st, rc);
+        prev = level;
     }
     if (hipError_t e = rt::launch_adaptive_resolve(a.planes, a.planes + 3u * texels, texels, band_width, P.tiles_x,
                                                    map->table + map->n_tiles, accum, out, sample_count, st);
         e != hipSuccess)
-        return abort(fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
+        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
     RT_HIP(hipEventRecord(map->ev_read, st));   // the next set call waits for this frame
     map->read_pending = true;
     return render_issued(ctx, st);

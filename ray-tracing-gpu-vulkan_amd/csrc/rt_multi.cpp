@@ -26,14 +26,18 @@
 // rows (rt_plan.h tile_row_parts; the stop criterion is per 8x8 tile), each part rendered on its
 // device's context by the resumable pass loop of rt_host.h, all parts' passes interleaved by the
 // calling thread; the gather adds each part's per-tile count table, and one fused kernel per part
-// stores accumulator, rgba8 and counts in place. They keep their own rows maps and buffers and
-// never touch the balancer.
+// stores accumulator, rgba8 and counts in place. They keep their own parts (the same Part struct
+// and buffer lifecycle, fit_part / free_part, as the plain frames') and never touch the balancer.
 //
-// A frame is a FramePlan (rt_plan.h): the partition and the ordered steps rt_multi_render executes.
-// The plan is host-only data, so the CPU tests check it for every device count and height without
-// a GPU (rt_debug_multi_plan*, tests/test_multi_plan.py). rt_debug_multi_create_logical runs the
-// same executor over N logical devices on GPU 0, with each send / receive pair a device copy
-// ordered by the same group boundaries, so the one-GPU pool executes every step of the N > 1 plan.
+// A frame is a FramePlan (rt_plan.h): the partition and the ordered steps. One executor (run_steps)
+// walks the steps of both frame kinds and owns the transport: the groups, the sends and receives
+// (wire_of names each one's buffer) over real RCCL ranks, logical copies or a one-rank
+// communicator, and the closing of a group after a failure; each kind supplies its parts and its
+// leaf steps (run_plan, run_adaptive). The plan is host-only data, so the CPU tests check it for
+// every device count and height without a GPU (rt_debug_multi_plan*, tests/test_multi_plan.py).
+// rt_debug_multi_create_logical runs the same executor over N logical devices on GPU 0, with each
+// send / receive pair (rt_plan.h pair_group) a device copy ordered by the same group boundaries, so
+// the one-GPU pool executes every step of the N > 1 plan.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -72,33 +76,26 @@ using namespace rt::plan;
 
 namespace {
 
-// One part of a multi-device frame on its device (its own context), with its buffers.
-struct Launch {
+// One part of a frame on its device: its rows maps and buffers. An adaptive frame
+// (rt_multi_render_adaptive; rt_plan.h tile_row_parts) keeps parts of its own, so a plain frame's
+// part is never rewritten by one.
+struct Part {
     uint32_t dev = 0;                    // logical device
     std::vector<uint32_t> rows;          // global rows, band order
     bool whole = false;
-    rt_context* ctx = nullptr;           // on dev
     uint32_t cap = 0;                    // rows the buffers below hold
     uint32_t* rows_dev = nullptr;        // rows on dev (the kernel's map)
     uint32_t* rows_root = nullptr;       // rows on device 0 (the row loads / stores)
     float* acc = nullptr;                // band on dev: rows x W float4 (not for a whole part)
     uint8_t* out = nullptr;              // band on dev: rows x W rgba8 (the kernel's store; not sent)
     float* stage_acc = nullptr;          // dev != 0: the band's copy on device 0
+    uint32_t* stage_counts = nullptr;    // adaptive, dev != 0: the band's per-tile counts on device 0
 };
 
-// One part of an adaptive frame (rt_multi_render_adaptive; rt_plan.h tile_row_parts) with its own
-// rows maps and buffers: a plain frame's Launch is never rewritten by an adaptive frame. The part
-// renders on the context of its device's Launch (no second context, no second scene).
-struct AdaptivePart {
-    uint32_t dev = 0;
-    std::vector<uint32_t> rows;          // global rows, band order: whole 8-row tile rows
-    bool whole = false;
-    uint32_t* rows_dev = nullptr;        // rows on dev (the kernel's map)
-    uint32_t* rows_root = nullptr;       // rows on device 0 (the store's map)
-    float* acc = nullptr;                // band on dev: rows x W float4
-    uint8_t* out = nullptr;              // band on dev: rows x W rgba8 (the band resolve's store; not sent)
-    float* stage_acc = nullptr;          // dev != 0: the band's copy on device 0
-    uint32_t* stage_counts = nullptr;    // dev != 0: the band's per-tile counts on device 0
+// A part of a plain frame with its device's context (its scene); an adaptive part renders on the
+// context of its device's Launch (no second context, no second scene).
+struct Launch : Part {
+    rt_context* ctx = nullptr;           // on dev
 };
 
 constexpr uint32_t kMaxLag = 8;  // strip frames the balancer keeps (its largest lag)
@@ -143,7 +140,7 @@ struct rt_multi {
     // adaptive frames: their own static partition (never re-dealt, no balancer record) and buffers
     struct AdaptiveFrames {
         uint32_t W = 0, H = 0;
-        std::vector<AdaptivePart> parts;         // one per plan part, same index
+        std::vector<Part> parts;                 // one per plan part, same index
         FramePlan plan;
         std::vector<rt_adaptive_info> info;      // per device, the last adaptive frame
     } ad;
@@ -153,27 +150,28 @@ namespace {
 
 int phys_of(const rt_multi* m, uint32_t dev) { return m->phys[dev]; }
 
-void free_buffers(rt_multi* m, Launch& l) {
+void free_part(rt_multi* m, Part& q) {
     {
-        DeviceGuard g(phys_of(m, l.dev));
+        DeviceGuard g(phys_of(m, q.dev));
         (void)hipDeviceSynchronize();
-        if (l.rows_dev) (void)hipFree(l.rows_dev);
-        if (l.acc) (void)hipFree(l.acc);
-        if (l.out) (void)hipFree(l.out);
+        if (q.rows_dev) (void)hipFree(q.rows_dev);
+        if (q.acc) (void)hipFree(q.acc);
+        if (q.out) (void)hipFree(q.out);
     }
     DeviceGuard g0(phys_of(m, 0));
     (void)hipDeviceSynchronize();
-    if (l.rows_root) (void)hipFree(l.rows_root);
-    if (l.stage_acc) (void)hipFree(l.stage_acc);
-    l.rows_dev = l.rows_root = nullptr;
-    l.acc = l.stage_acc = nullptr;
-    l.out = nullptr;
-    l.cap = 0;
+    if (q.rows_root) (void)hipFree(q.rows_root);
+    if (q.stage_acc) (void)hipFree(q.stage_acc);
+    if (q.stage_counts) (void)hipFree(q.stage_counts);
+    q.rows_dev = q.rows_root = q.stage_counts = nullptr;
+    q.acc = q.stage_acc = nullptr;
+    q.out = nullptr;
+    q.cap = 0;
 }
 
 void free_launches(rt_multi* m) {
     for (Launch& l : m->launches) {
-        free_buffers(m, l);
+        free_part(m, l);
         DeviceGuard g(phys_of(m, l.dev));
         rt_context_destroy(l.ctx);
     }
@@ -205,34 +203,45 @@ int set_scene_all(rt_multi* m) {
     return rc;
 }
 
-// The part's buffers for its rows (grown, never shrunk; a move of a few rows reuses them), and its
-// rows maps on its device and on device 0. Callers have drained the streams that read them.
-int fit_buffers(rt_multi* m, Launch& l) {
-    const uint32_t nr = uint32_t(l.rows.size()), W = m->W;
-    if (!nr || l.whole) return RT_OK;
-    if (l.cap < nr) {
-        free_buffers(m, l);
-        // room for the rows a balancer moves in (a few percent of a band) without reallocating
-        const uint32_t cap = std::min<uint32_t>(m->H, nr + std::max<uint32_t>(kStrip, nr / 16));
+// The part's buffers for its rows of a W-wide image (grown to `room` rows, never shrunk: a move of
+// a few rows reuses them), with a count stage for a remote part when `counts`, and its rows maps on
+// its device and on device 0. Callers have drained the streams that read them.
+int fit_part(rt_multi* m, Part& q, uint32_t W, uint32_t room, bool counts) {
+    const uint32_t nr = uint32_t(q.rows.size());
+    if (!nr || q.whole) return RT_OK;
+    if (q.cap < nr) {
+        free_part(m, q);
+        const uint32_t cap = std::max(room, nr);
         const size_t texels = size_t(cap) * W;
         {
-            DeviceGuard g(phys_of(m, l.dev));
-            RT_HIP(hipMalloc(&l.rows_dev, size_t(cap) * 4));
-            RT_HIP(hipMalloc(&l.acc, texels * 16));
-            RT_HIP(hipMalloc(&l.out, texels * 4));
+            DeviceGuard g(phys_of(m, q.dev));
+            RT_HIP(hipMalloc(&q.rows_dev, size_t(cap) * 4));
+            RT_HIP(hipMalloc(&q.acc, texels * 16));
+            RT_HIP(hipMalloc(&q.out, texels * 4));
         }
         DeviceGuard g0(phys_of(m, 0));
-        RT_HIP(hipMalloc(&l.rows_root, size_t(cap) * 4));
-        if (l.dev != 0) RT_HIP(hipMalloc(&l.stage_acc, texels * 16));
-        l.cap = cap;
+        RT_HIP(hipMalloc(&q.rows_root, size_t(cap) * 4));
+        if (q.dev != 0) RT_HIP(hipMalloc(&q.stage_acc, texels * 16));
+        if (q.dev != 0 && counts) {
+            const size_t tiles = ((size_t(W) + kStrip - 1) / kStrip) * ((size_t(cap) + kStrip - 1) / kStrip);
+            RT_HIP(hipMalloc(&q.stage_counts, tiles * 4));
+        }
+        q.cap = cap;
     }
     {
-        DeviceGuard g(phys_of(m, l.dev));
-        RT_HIP(hipMemcpy(l.rows_dev, l.rows.data(), size_t(nr) * 4, hipMemcpyHostToDevice));
+        DeviceGuard g(phys_of(m, q.dev));
+        RT_HIP(hipMemcpy(q.rows_dev, q.rows.data(), size_t(nr) * 4, hipMemcpyHostToDevice));
     }
     DeviceGuard g0(phys_of(m, 0));
-    RT_HIP(hipMemcpy(l.rows_root, l.rows.data(), size_t(nr) * 4, hipMemcpyHostToDevice));
+    RT_HIP(hipMemcpy(q.rows_root, q.rows.data(), size_t(nr) * 4, hipMemcpyHostToDevice));
     return RT_OK;
+}
+
+// A strip part's buffers: room for the rows a balancer moves in (a few percent of a band) without
+// reallocating.
+int fit_launch(rt_multi* m, Launch& l) {
+    const uint32_t nr = uint32_t(l.rows.size());
+    return fit_part(m, l, m->W, std::min<uint32_t>(m->H, nr + std::max<uint32_t>(kStrip, nr / 16)), false);
 }
 
 // (Re)builds the launches for `key` from the partition: one per part (device + global rows), its
@@ -256,7 +265,7 @@ int set_partition(rt_multi* m, const std::string& key, uint32_t W, uint32_t H, P
     for (Launch& l : m->launches) {
         if (int rc = rt_context_create(phys_of(m, l.dev), &l.ctx)) return rc;
         if (m->launches.size() > 1) rt::keep_row_weights(l.ctx);   // the balancer reads them
-        if (int rc = fit_buffers(m, l)) return rc;
+        if (int rc = fit_launch(m, l)) return rc;
     }
     m->key = key;
     return m->scene_set ? set_scene_all(m) : RT_OK;
@@ -277,7 +286,7 @@ int repartition(rt_multi* m, const Parts& parts) {
         Launch& l = m->launches[i];
         l.rows = m->plan[0].parts[i].rows;
         l.whole = m->plan[0].parts[i].whole;
-        if (int rc = fit_buffers(m, l)) return rc;
+        if (int rc = fit_launch(m, l)) return rc;
     }
     return RT_OK;
 }
@@ -332,36 +341,6 @@ int balance_step(rt_multi* m) {
     return repartition(m, next);
 }
 
-// A send / receive pair of the logical transport (one GPU): a device copy on the receiver's stream
-// after the sender's earlier work, and the sender's later work after the copy.
-int logical_transfers(rt_multi* m, const std::vector<PlanStep>& group) {
-    size_t ev = 0;
-    for (const PlanStep& r : group) {
-        if (r.op != OP_RECV) continue;
-        const PlanStep* s = nullptr;
-        for (const PlanStep& c : group)
-            if (c.op == OP_SEND && c.dev == r.peer && c.peer == r.dev && c.part == r.part) s = &c;
-        if (!s || s->count != r.count) return fail(RT_ERR_INVALID_ARGUMENT, "unpaired receive in the plan");
-        Launch& l = m->launches[r.part];
-        const float* src = s->dev == 0 ? l.stage_acc : l.acc;
-        float* dst = r.dev == 0 ? l.stage_acc : l.acc;
-        while (m->xev.size() < ev + 2) {
-            hipEvent_t e = nullptr;
-            DeviceGuard g(phys_of(m, 0));
-            RT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            m->xev.push_back(e);
-        }
-        DeviceGuard g(phys_of(m, r.dev));
-        RT_HIP(hipEventRecord(m->xev[ev], m->stream[s->dev]));
-        RT_HIP(hipStreamWaitEvent(m->stream[r.dev], m->xev[ev], 0));
-        RT_HIP(hipMemcpyAsync(dst, src, r.count * 4, hipMemcpyDeviceToDevice, m->stream[r.dev]));
-        RT_HIP(hipEventRecord(m->xev[ev + 1], m->stream[r.dev]));
-        RT_HIP(hipStreamWaitEvent(m->stream[s->dev], m->xev[ev + 1], 0));
-        ev += 2;
-    }
-    return RT_OK;
-}
-
 // The rgba8 resolve of the whole accumulator: one launch when every part shares one spp, else each
 // part's contiguous row runs with its own RenderCallInfo's spp (rt_render's bands).
 int resolve_all(rt_multi* m, rt_context* c0, const RenderCallInfo* rcis, size_t n_rci, float* acc, uint8_t* out) {
@@ -406,52 +385,103 @@ int self_group_fence(rt_multi* m, bool before) {
     return RT_OK;
 }
 
-// A context on device 0 (the row loads / stores and the resolve run on stream[0]).
-rt_context* root_ctx(rt_multi* m) {
+// The context of logical device `dev`: its Launch's (the strip partition has one per device).
+rt_context* ctx_of(rt_multi* m, uint32_t dev) {
     for (Launch& l : m->launches)
-        if (l.dev == 0) return l.ctx;
+        if (l.dev == dev) return l.ctx;
     return nullptr;
 }
 
-// Executes a frame plan: rcis[i] for part i (n_rci == 1: rcis[0] for every part; offsets replaced
-// by the rows maps), into the caller's acc / out (device 0, W x H). Every step is queued on its
-// device's stream; the stream order of each device and the RCCL groups order them across devices.
-int run_plan(rt_multi* m, const FramePlan& p, const RenderCallInfo* rcis, size_t n_rci, const rt_options* opt,
-             float* acc, uint8_t* out) {
-    const uint32_t W = m->W, H = m->H;
-    rt_context* c0 = root_ctx(m);
+// The buffer a transfer step names on s.dev, with its element type (4 bytes each): of the part's
+// accumulator, its stage on device 0 and its band on its own device; of its count table, the send
+// reads its device's context's table and the receive fills the count stage on device 0.
+struct Wire {
+    void* buf = nullptr;
+    ncclDataType_t type = ncclFloat32;
+};
+int wire_of(rt_multi* m, const PlanStep& s, Part& q, Wire* w) {
+    if (s.op == OP_SEND || s.op == OP_RECV) {
+        *w = Wire{s.dev == 0 ? q.stage_acc : q.acc, ncclFloat32};
+    } else if (s.op == OP_SEND_COUNTS) {
+        rt_context* c = ctx_of(m, s.dev);
+        if (!c) return fail(RT_ERR_INVALID_ARGUMENT, "no context on a device of the plan");
+        *w = Wire{const_cast<uint32_t*>(rt::adaptive_tile_counts(c)), ncclUint32};
+    } else {
+        if (s.dev != 0) return fail(RT_ERR_INVALID_ARGUMENT, "a count receive off device 0 in the plan");
+        *w = Wire{q.stage_counts, ncclUint32};
+    }
+    return RT_OK;
+}
+
+// A group of the logical transport (one GPU), steps[k] naming wires[k]: each send / receive pair
+// (rt_plan.h pair_group) is a device copy on the receiver's stream after the sender's earlier work,
+// and the sender's later work after the copy.
+int logical_transfers(rt_multi* m, const PlanStep* steps, size_t n, const std::vector<void*>& wires) {
+    std::vector<std::pair<size_t, size_t>> pairs;
+    if (wires.size() != n || !pair_group(steps, n, pairs))
+        return fail(RT_ERR_INVALID_ARGUMENT, "unpaired receive in the plan");
+    size_t ev = 0;
+    for (const auto& pr : pairs) {
+        const PlanStep &r = steps[pr.first], &s = steps[pr.second];
+        while (m->xev.size() < ev + 2) {
+            hipEvent_t e = nullptr;
+            DeviceGuard g(phys_of(m, 0));
+            RT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            m->xev.push_back(e);
+        }
+        DeviceGuard g(phys_of(m, r.dev));
+        RT_HIP(hipEventRecord(m->xev[ev], m->stream[s.dev]));
+        RT_HIP(hipStreamWaitEvent(m->stream[r.dev], m->xev[ev], 0));
+        RT_HIP(hipMemcpyAsync(wires[pr.first], wires[pr.second], r.count * 4, hipMemcpyDeviceToDevice, m->stream[r.dev]));
+        RT_HIP(hipEventRecord(m->xev[ev + 1], m->stream[r.dev]));
+        RT_HIP(hipStreamWaitEvent(m->stream[s.dev], m->xev[ev + 1], 0));
+        ev += 2;
+    }
+    return RT_OK;
+}
+
+// Executes a frame plan's steps from `first` on: the groups and transfers here, over real RCCL
+// ranks, logical copies or the one-rank communicator; every other step by the frame kind's
+// `leaf(step, part)`, with `part_of(i)` the kind's part i. Every step is queued on its device's
+// stream; the stream order of each device and the groups order them across devices.
+template <class PartOf, class Leaf>
+int run_steps(rt_multi* m, const FramePlan& p, size_t first, PartOf part_of, Leaf leaf) {
+    const bool copies = m->logical && !m->self_rccl;
     bool in_group = false;
-    std::vector<PlanStep> group;   // logical transport: the group's sends / receives
+    size_t group_at = 0;          // copies: the open group's first transfer step,
+    std::vector<void*> wires;     // and each transfer's buffer
     auto body = [&]() -> int {
-        for (const PlanStep& s : p.steps) {
-            Launch& l = m->launches[s.part];
-            float* dev_buf = s.dev == 0 ? l.stage_acc : l.acc;   // a SEND / RECV's buffer on s.dev
-            float* root_buf = l.dev == 0 ? l.acc : l.stage_acc;  // the part's accumulator on device 0
-            const uint32_t nr = uint32_t(l.rows.size());
+        for (size_t i = first; i < p.steps.size(); i++) {
+            const PlanStep& s = p.steps[i];
             switch (s.op) {
                 case OP_GROUP_START:
                     if (m->self_rccl) {   // stream[0] carries the group: after every device's work so far
                         if (int rc = self_group_fence(m, true)) return rc;
                     }
-                    if (!m->logical || m->self_rccl) RT_NCCL(ncclGroupStart());
-                    group.clear();
+                    if (!copies) RT_NCCL(ncclGroupStart());
+                    group_at = i + 1;
+                    wires.clear();
                     in_group = true;
                     break;
                 case OP_GROUP_END:
                     in_group = false;
-                    if (m->logical && !m->self_rccl) {
-                        if (int rc = logical_transfers(m, group)) return rc;
-                    } else {
-                        RT_NCCL(ncclGroupEnd());
-                        if (m->self_rccl) {   // every device's later work after the group
-                            if (int rc = self_group_fence(m, false)) return rc;
-                        }
+                    if (copies) {
+                        if (int rc = logical_transfers(m, p.steps.data() + group_at, i - group_at, wires)) return rc;
+                        break;
+                    }
+                    RT_NCCL(ncclGroupEnd());
+                    if (m->self_rccl) {   // every device's later work after the group
+                        if (int rc = self_group_fence(m, false)) return rc;
                     }
                     break;
                 case OP_SEND:
-                case OP_RECV: {
-                    if (m->logical && !m->self_rccl) {
-                        group.push_back(s);
+                case OP_RECV:
+                case OP_SEND_COUNTS:
+                case OP_RECV_COUNTS: {
+                    Wire w;
+                    if (int rc = wire_of(m, s, part_of(s.part), &w)) return rc;
+                    if (copies) {
+                        wires.push_back(w.buf);
                         break;
                     }
                     // a one-rank communicator (self_rccl): every transfer is rank 0 to itself on
@@ -461,80 +491,70 @@ int run_plan(rt_multi* m, const FramePlan& p, const RenderCallInfo* rcis, size_t
                     const int peer = m->self_rccl ? 0 : int(s.peer);
                     DeviceGuard g(phys_of(m, rank_dev));
                     const ncclResult_t e =
-                        s.op == OP_SEND
-                            ? ncclSend(dev_buf, s.count, ncclFloat32, peer, m->comm[rank_dev], m->stream[rank_dev])
-                            : ncclRecv(dev_buf, s.count, ncclFloat32, peer, m->comm[rank_dev], m->stream[rank_dev]);
+                        s.op == OP_SEND || s.op == OP_SEND_COUNTS
+                            ? ncclSend(w.buf, s.count, w.type, peer, m->comm[rank_dev], m->stream[rank_dev])
+                            : ncclRecv(w.buf, s.count, w.type, peer, m->comm[rank_dev], m->stream[rank_dev]);
                     if (e != ncclSuccess) return fail(RT_ERR_DEVICE, std::string("RCCL: ") + ncclGetErrorString(e));
                     break;
                 }
-                case OP_LOAD_ROWS:
-                    if (int rc = rt_gather_rows(c0, acc, l.rows_root, nr, W, H, root_buf, m->stream[0])) return rc;
-                    break;
-                case OP_STORE_ROWS:
-                    if (int rc = rt_scatter_rows(c0, root_buf, nullptr, l.rows_root, nr, W, H, acc, nullptr,
-                                                 m->stream[0]))
-                        return rc;
-                    break;
-                case OP_RENDER: {
-                    RenderCallInfo r = rcis[n_rci == 1 ? 0 : s.part];
-                    r.offset = rt_uvec2{0, 0};   // the rows map carries the global rows
-                    const bool d = (s.flags & kDirect) != 0;
-                    if (int rc = rt_render_device(l.ctx, &r, d ? nullptr : l.rows_dev, W, nr, d ? acc : l.acc,
-                                                  d ? out : l.out, opt, m->stream[l.dev]))
-                        return rc;
-                    break;
-                }
-                case OP_RESOLVE:
-                    if (int rc = resolve_all(m, c0, rcis, n_rci, acc, out)) return rc;
-                    break;
                 default:
-                    return fail(RT_ERR_INVALID_ARGUMENT, "bad plan step");
+                    if (int rc = leaf(s, part_of(s.part))) return rc;
             }
         }
         return RT_OK;
     };
     const int rc = body();
-    if (in_group && (!m->logical || m->self_rccl)) (void)ncclGroupEnd();   // a failure inside a group still closes it
+    if (in_group && !copies) (void)ncclGroupEnd();   // a failure inside a group still closes it
     return rc;
+}
+
+// A plain frame: rcis[i] for part i (n_rci == 1: rcis[0] for every part; offsets replaced by the
+// rows maps), into the caller's acc / out (device 0, W x H).
+int run_plan(rt_multi* m, const FramePlan& p, const RenderCallInfo* rcis, size_t n_rci, const rt_options* opt,
+             float* acc, uint8_t* out) {
+    const uint32_t W = m->W, H = m->H;
+    rt_context* c0 = ctx_of(m, 0);   // the row loads / stores and the resolve run on stream[0]
+    auto leaf = [&](const PlanStep& s, Launch& l) -> int {
+        float* root_buf = l.dev == 0 ? l.acc : l.stage_acc;   // the part's accumulator on device 0
+        const uint32_t nr = uint32_t(l.rows.size());
+        switch (s.op) {
+            case OP_LOAD_ROWS:
+                return rt_gather_rows(c0, acc, l.rows_root, nr, W, H, root_buf, m->stream[0]);
+            case OP_STORE_ROWS:
+                return rt_scatter_rows(c0, root_buf, nullptr, l.rows_root, nr, W, H, acc, nullptr, m->stream[0]);
+            case OP_RENDER: {
+                RenderCallInfo r = rcis[n_rci == 1 ? 0 : s.part];
+                r.offset = rt_uvec2{0, 0};   // the rows map carries the global rows
+                const bool d = (s.flags & kDirect) != 0;
+                return rt_render_device(l.ctx, &r, d ? nullptr : l.rows_dev, W, nr, d ? acc : l.acc, d ? out : l.out,
+                                        opt, m->stream[l.dev]);
+            }
+            case OP_RESOLVE:
+                return resolve_all(m, c0, rcis, n_rci, acc, out);
+            default:
+                return fail(RT_ERR_INVALID_ARGUMENT, "bad plan step");
+        }
+    };
+    return run_steps(m, p, 0, [&](uint32_t i) -> Launch& { return m->launches[i]; }, leaf);
 }
 
 // ---- adaptive frames ---------------------------------------------------------------------------
 
-// The context of logical device `dev`: its Launch's (the strip partition has one per device).
-rt_context* ctx_of(rt_multi* m, uint32_t dev) {
-    for (Launch& l : m->launches)
-        if (l.dev == dev) return l.ctx;
-    return nullptr;
-}
-
-void free_adaptive(rt_multi* m) {
-    for (AdaptivePart& p : m->ad.parts) {
-        {
-            DeviceGuard g(phys_of(m, p.dev));
-            (void)hipDeviceSynchronize();
-            if (p.rows_dev) (void)hipFree(p.rows_dev);
-            if (p.acc) (void)hipFree(p.acc);
-            if (p.out) (void)hipFree(p.out);
-        }
-        DeviceGuard g0(phys_of(m, 0));
-        (void)hipDeviceSynchronize();
-        if (p.rows_root) (void)hipFree(p.rows_root);
-        if (p.stage_acc) (void)hipFree(p.stage_acc);
-        if (p.stage_counts) (void)hipFree(p.stage_counts);
-    }
+void clear_adaptive(rt_multi* m) {
+    for (Part& q : m->ad.parts) free_part(m, q);
     m->ad.parts.clear();
     m->ad.plan = FramePlan{};
     m->ad.W = m->ad.H = 0;
 }
 
-// The tile-row parts of a W x H adaptive frame, their buffers and the frame's plan. Same size:
-// nothing to do (the deal is static).
+// The tile-row parts of a W x H adaptive frame, their buffers (exact: the deal is static) and the
+// frame's plan. Same size: nothing to do.
 int set_adaptive_partition(rt_multi* m, uint32_t W, uint32_t H) {
     if (m->ad.W == W && m->ad.H == H && !m->ad.parts.empty()) return RT_OK;
-    free_adaptive(m);
+    clear_adaptive(m);
     m->ad.plan = make_adaptive_plan(W, H, tile_row_parts(m->n, H));
     for (const PlanPart& q : m->ad.plan.parts) {
-        AdaptivePart p;
+        Part p;
         p.dev = q.dev;
         p.rows = q.rows;
         p.whole = q.whole;
@@ -542,25 +562,8 @@ int set_adaptive_partition(rt_multi* m, uint32_t W, uint32_t H) {
     }
     m->ad.W = W;
     m->ad.H = H;
-    const size_t tiles_x = (size_t(W) + kStrip - 1) / kStrip;
-    for (AdaptivePart& p : m->ad.parts) {
-        const size_t nr = p.rows.size(), texels = nr * W;
-        if (!nr || p.whole) continue;
-        {
-            DeviceGuard g(phys_of(m, p.dev));
-            RT_HIP(hipMalloc(&p.rows_dev, nr * 4));
-            RT_HIP(hipMalloc(&p.acc, texels * 16));
-            RT_HIP(hipMalloc(&p.out, texels * 4));
-            RT_HIP(hipMemcpy(p.rows_dev, p.rows.data(), nr * 4, hipMemcpyHostToDevice));
-        }
-        DeviceGuard g0(phys_of(m, 0));
-        RT_HIP(hipMalloc(&p.rows_root, nr * 4));
-        RT_HIP(hipMemcpy(p.rows_root, p.rows.data(), nr * 4, hipMemcpyHostToDevice));
-        if (p.dev != 0) {
-            RT_HIP(hipMalloc(&p.stage_acc, texels * 16));
-            RT_HIP(hipMalloc(&p.stage_counts, tiles_x * ((nr + kStrip - 1) / kStrip) * 4));
-        }
-    }
+    for (Part& p : m->ad.parts)
+        if (int rc = fit_part(m, p, W, uint32_t(p.rows.size()), true)) return rc;
     return RT_OK;
 }
 
@@ -582,13 +585,13 @@ int render_adaptive_parts(rt_multi* m, const std::vector<PlanStep>& renders, con
                                          m->stream[0]);
     }
     struct Run {
-        AdaptivePart* p;
+        Part* p;
         rt_context* ctx;
         bool live;
     };
     std::vector<Run> runs;
     for (const PlanStep& s : renders) {
-        AdaptivePart& p = m->ad.parts[s.part];
+        Part& p = m->ad.parts[s.part];
         rt_context* c = ctx_of(m, p.dev);
         if (!c) return fail(RT_ERR_INVALID_ARGUMENT, "no context on a device of the plan");
         bool empty = false;
@@ -635,115 +638,48 @@ int render_adaptive_parts(rt_multi* m, const std::vector<PlanStep>& renders, con
     return rc;
 }
 
-// A send / receive pair of an adaptive frame's group on the logical transport: as
-// logical_transfers, for the accumulator bands and the count tables.
-int adaptive_logical_transfers(rt_multi* m, const std::vector<PlanStep>& group) {
-    size_t ev = 0;
-    for (const PlanStep& r : group) {
-        if (r.op != OP_RECV && r.op != OP_RECV_COUNTS) continue;
-        const uint32_t send_op = r.op == OP_RECV ? uint32_t(OP_SEND) : uint32_t(OP_SEND_COUNTS);
-        const PlanStep* s = nullptr;
-        for (const PlanStep& c : group)
-            if (c.op == send_op && c.dev == r.peer && c.peer == r.dev && c.part == r.part) s = &c;
-        if (!s || s->count != r.count || r.dev != 0) return fail(RT_ERR_INVALID_ARGUMENT, "unpaired receive in the plan");
-        AdaptivePart& p = m->ad.parts[r.part];
-        const void* src = r.op == OP_RECV ? static_cast<const void*>(p.acc)
-                                          : static_cast<const void*>(rt::adaptive_tile_counts(ctx_of(m, p.dev)));
-        void* dst = r.op == OP_RECV ? static_cast<void*>(p.stage_acc) : static_cast<void*>(p.stage_counts);
-        while (m->xev.size() < ev + 2) {
-            hipEvent_t e = nullptr;
-            DeviceGuard g(phys_of(m, 0));
-            RT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            m->xev.push_back(e);
-        }
-        DeviceGuard g(phys_of(m, r.dev));
-        RT_HIP(hipEventRecord(m->xev[ev], m->stream[s->dev]));
-        RT_HIP(hipStreamWaitEvent(m->stream[r.dev], m->xev[ev], 0));
-        RT_HIP(hipMemcpyAsync(dst, src, r.count * 4, hipMemcpyDeviceToDevice, m->stream[r.dev]));
-        RT_HIP(hipEventRecord(m->xev[ev + 1], m->stream[r.dev]));
-        RT_HIP(hipStreamWaitEvent(m->stream[s->dev], m->xev[ev + 1], 0));
-        ev += 2;
-    }
+// An adaptive frame's plan (make_adaptive_plan) into the caller's buffers on device 0.
+int run_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, const rt_adaptive* ad, float* acc,
+                 uint8_t* out, uint32_t* sample_count) {
+    const FramePlan& p = m->ad.plan;
+    const uint32_t W = m->ad.W, H = m->ad.H;
+    size_t i = 0;
+    std::vector<PlanStep> renders;   // the plan's leading steps: every part's passes, interleaved
+    for (; i < p.steps.size() && p.steps[i].op == OP_RENDER_ADAPTIVE; i++) renders.push_back(p.steps[i]);
+    if (int rc = render_adaptive_parts(m, renders, rci, opt, ad, acc, out, sample_count)) return rc;
+    auto leaf = [&](const PlanStep& s, Part& q) -> int {
+        if (s.op != OP_STORE_TILES) return fail(RT_ERR_INVALID_ARGUMENT, "bad plan step");
+        const float* src = q.dev == 0 ? q.acc : q.stage_acc;
+        const uint32_t* counts = q.dev == 0 ? rt::adaptive_tile_counts(ctx_of(m, 0)) : q.stage_counts;
+        return rt::adaptive_store_tiles(phys_of(m, 0), src, uint32_t(q.rows.size()), W, counts, q.rows_root, H, acc, out,
+                                        sample_count, m->stream[0]);
+    };
+    return run_steps(m, p, i, [&](uint32_t k) -> Part& { return m->ad.parts[k]; }, leaf);
+}
+
+// What every frame entry point `who` checks first.
+int frame_check(const rt_multi* m, const RenderCallInfo* rci, const float* accum, const uint8_t* out, const char* who) {
+    if (!m || !rci) return fail(RT_ERR_INVALID_ARGUMENT, "m or rci is NULL");
+    if (!m->scene_set) return fail(RT_ERR_NO_SCENE, std::string(who) + " before rt_multi_set_scene");
+    if (rci->image_size.x == 0 || rci->image_size.y == 0) return fail(RT_ERR_INVALID_ARGUMENT, "image_size is zero");
+    if (!accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "accum or out is NULL");
     return RT_OK;
 }
 
-// Executes an adaptive frame's plan (make_adaptive_plan) into the caller's buffers on device 0.
-int run_adaptive_plan(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, const rt_adaptive* ad,
-                      float* acc, uint8_t* out, uint32_t* sample_count) {
-    const FramePlan& p = m->ad.plan;
-    const uint32_t W = m->ad.W, H = m->ad.H;
-    bool in_group = false;
-    std::vector<PlanStep> group;   // logical transport: the group's sends / receives
-    auto body = [&]() -> int {
-        size_t i = 0;
-        std::vector<PlanStep> renders;   // the plan's leading steps: every part's passes, interleaved
-        for (; i < p.steps.size() && p.steps[i].op == OP_RENDER_ADAPTIVE; i++) renders.push_back(p.steps[i]);
-        if (int rc = render_adaptive_parts(m, renders, rci, opt, ad, acc, out, sample_count)) return rc;
-        for (; i < p.steps.size(); i++) {
-            const PlanStep& s = p.steps[i];
-            AdaptivePart& q = m->ad.parts[s.part];
-            const uint32_t nr = uint32_t(q.rows.size());
-            switch (s.op) {
-                case OP_GROUP_START:
-                    if (m->self_rccl) {
-                        if (int rc = self_group_fence(m, true)) return rc;
-                    }
-                    if (!m->logical || m->self_rccl) RT_NCCL(ncclGroupStart());
-                    group.clear();
-                    in_group = true;
-                    break;
-                case OP_GROUP_END:
-                    in_group = false;
-                    if (m->logical && !m->self_rccl) {
-                        if (int rc = adaptive_logical_transfers(m, group)) return rc;
-                    } else {
-                        RT_NCCL(ncclGroupEnd());
-                        if (m->self_rccl) {
-                            if (int rc = self_group_fence(m, false)) return rc;
-                        }
-                    }
-                    break;
-                case OP_SEND:
-                case OP_RECV:
-                case OP_SEND_COUNTS:
-                case OP_RECV_COUNTS: {
-                    if (m->logical && !m->self_rccl) {
-                        group.push_back(s);
-                        break;
-                    }
-                    // (self_rccl: rank 0 to itself on stream[0], the k-th send with the k-th receive)
-                    const uint32_t rank_dev = m->self_rccl ? 0u : s.dev;
-                    const int peer = m->self_rccl ? 0 : int(s.peer);
-                    const bool counts = s.op == OP_SEND_COUNTS || s.op == OP_RECV_COUNTS;
-                    const bool send = s.op == OP_SEND || s.op == OP_SEND_COUNTS;
-                    // a send reads the part's band / its context's tile table, a receive fills device 0's stages
-                    void* buf = counts ? (send ? const_cast<uint32_t*>(rt::adaptive_tile_counts(ctx_of(m, q.dev)))
-                                               : q.stage_counts)
-                                       : (send ? static_cast<void*>(q.acc) : static_cast<void*>(q.stage_acc));
-                    const ncclDataType_t ty = counts ? ncclUint32 : ncclFloat32;
-                    DeviceGuard g(phys_of(m, rank_dev));
-                    const ncclResult_t e = send ? ncclSend(buf, s.count, ty, peer, m->comm[rank_dev], m->stream[rank_dev])
-                                                : ncclRecv(buf, s.count, ty, peer, m->comm[rank_dev], m->stream[rank_dev]);
-                    if (e != ncclSuccess) return fail(RT_ERR_DEVICE, std::string("RCCL: ") + ncclGetErrorString(e));
-                    break;
-                }
-                case OP_STORE_TILES: {
-                    const float* src = q.dev == 0 ? q.acc : q.stage_acc;
-                    const uint32_t* counts = q.dev == 0 ? rt::adaptive_tile_counts(ctx_of(m, 0)) : q.stage_counts;
-                    if (int rc = rt::adaptive_store_tiles(phys_of(m, 0), src, nr, W, counts, q.rows_root, H, acc, out,
-                                                          sample_count, m->stream[0]))
-                        return rc;
-                    break;
-                }
-                default:
-                    return fail(RT_ERR_INVALID_ARGUMENT, "bad plan step");
-            }
-        }
-        return RT_OK;
-    };
-    const int rc = body();
-    if (in_group && (!m->logical || m->self_rccl)) (void)ncclGroupEnd();   // a failure inside a group still closes it
-    return rc;
+// A frame starts on every device's stream after the caller's earlier work on `st` (device 0) ...
+int frame_begin(rt_multi* m, hipStream_t st) {
+    DeviceGuard g0(phys_of(m, 0));
+    RT_HIP(hipEventRecord(m->ev_in, st));
+    for (uint32_t d = 0; d < m->n; d++) RT_HIP(hipStreamWaitEvent(m->stream[d], m->ev_in, 0));
+    return RT_OK;
+}
+
+// ... and the caller's later work on `st` waits for its last step on stream[0].
+int frame_end(rt_multi* m, hipStream_t st) {
+    DeviceGuard g0(phys_of(m, 0));
+    RT_HIP(hipEventRecord(m->ev_out, m->stream[0]));
+    RT_HIP(hipStreamWaitEvent(st, m->ev_out, 0));
+    return RT_OK;
 }
 
 int copy_plan(std::vector<uint32_t>&& v, uint32_t* out, uint64_t capacity, uint64_t* count) {
@@ -830,7 +766,7 @@ int rt_debug_multi_create_logical_rccl(uint32_t n_devices, rt_multi** out) {
 
 int rt_multi_destroy(rt_multi* m) {
     if (!m) return RT_OK;
-    if (!m->phys.empty()) free_adaptive(m);
+    if (!m->phys.empty()) clear_adaptive(m);
     if (!m->phys.empty()) free_launches(m);
     for (uint32_t d = 0; d < m->n && d < m->phys.size(); d++) {
         DeviceGuard g(phys_of(m, d));
@@ -872,11 +808,8 @@ int rt_multi_set_scene(rt_multi* m, const Sphere* spheres, uint32_t count) {
 
 int rt_multi_render(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, float* accum,
                     uint8_t* out, void* stream) {
-    if (!m || !rci) return fail(RT_ERR_INVALID_ARGUMENT, "m or rci is NULL");
-    if (!m->scene_set) return fail(RT_ERR_NO_SCENE, "rt_multi_render before rt_multi_set_scene");
+    if (int rc = frame_check(m, rci, accum, out, "rt_multi_render")) return rc;
     const uint32_t W = rci->image_size.x, H = rci->image_size.y;
-    if (W == 0 || H == 0) return fail(RT_ERR_INVALID_ARGUMENT, "image_size is zero");
-    if (!accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "accum or out is NULL");
     try {
         if (int rc = set_partition(m, "strips", W, H, strip_parts(m->n, H))) return rc;
         if (int rc = balance_step(m)) return rc;
@@ -884,11 +817,7 @@ int rt_multi_render(rt_multi* m, const RenderCallInfo* rci, const rt_options* op
         return fail(RT_ERR_OUT_OF_MEMORY, e.what());
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {   // the frame starts after the caller's earlier work on `stream` (device 0)
-        DeviceGuard g0(phys_of(m, 0));
-        RT_HIP(hipEventRecord(m->ev_in, st));
-        for (uint32_t d = 0; d < m->n; d++) RT_HIP(hipStreamWaitEvent(m->stream[d], m->ev_in, 0));
-    }
+    if (int rc = frame_begin(m, st)) return rc;
     const bool acc_mode = opt && opt->accumulate;
     if (int rc = run_plan(m, m->plan[acc_mode ? 1 : 0], rci, 1, opt, accum, out)) return rc;
     try {   // the balancer's record of this frame
@@ -902,20 +831,14 @@ int rt_multi_render(rt_multi* m, const RenderCallInfo* rci, const rt_options* op
     } catch (const std::exception& e) {
         return fail(RT_ERR_OUT_OF_MEMORY, e.what());
     }
-    DeviceGuard g0(phys_of(m, 0));
-    RT_HIP(hipEventRecord(m->ev_out, m->stream[0]));   // the caller's later work waits for it
-    RT_HIP(hipStreamWaitEvent(st, m->ev_out, 0));
-    return RT_OK;
+    return frame_end(m, st);
 }
 
 int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_options* opt, const rt_adaptive* ad,
                              float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info, void* stream) {
     if (info) std::memset(info, 0, sizeof(*info));
-    if (!m || !rci) return fail(RT_ERR_INVALID_ARGUMENT, "m or rci is NULL");
-    if (!m->scene_set) return fail(RT_ERR_NO_SCENE, "rt_multi_render_adaptive before rt_multi_set_scene");
+    if (int rc = frame_check(m, rci, accum, out, "rt_multi_render_adaptive")) return rc;
     const uint32_t W = rci->image_size.x, H = rci->image_size.y;
-    if (W == 0 || H == 0) return fail(RT_ERR_INVALID_ARGUMENT, "image_size is zero");
-    if (!accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "accum or out is NULL");
     {   // what needs no context is refused before anything is set up
         rt_options o;
         std::memset(&o, 0, sizeof(o));
@@ -928,7 +851,7 @@ int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_op
         if (int rc = set_partition(m, "strips", W, H, strip_parts(m->n, H))) return rc;
         if (int rc = set_adaptive_partition(m, W, H)) {
             const std::string msg = rt::g_last_error;
-            free_adaptive(m);
+            clear_adaptive(m);
             rt::g_last_error = msg;
             return rc;
         }
@@ -937,14 +860,10 @@ int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_op
         return fail(RT_ERR_OUT_OF_MEMORY, e.what());
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    {   // the frame starts after the caller's earlier work on `stream` (device 0)
-        DeviceGuard g0(phys_of(m, 0));
-        RT_HIP(hipEventRecord(m->ev_in, st));
-        for (uint32_t d = 0; d < m->n; d++) RT_HIP(hipStreamWaitEvent(m->stream[d], m->ev_in, 0));
-    }
+    if (int rc = frame_begin(m, st)) return rc;
     int rc;
     try {
-        rc = run_adaptive_plan(m, rci, opt, ad, accum, out, sample_count);
+        rc = run_adaptive(m, rci, opt, ad, accum, out, sample_count);
     } catch (const std::exception& e) {
         rc = fail(RT_ERR_OUT_OF_MEMORY, e.what());
     }
@@ -957,10 +876,7 @@ int rt_multi_render_adaptive(rt_multi* m, const RenderCallInfo* rci, const rt_op
             info->samples += d.samples;
         }
     }
-    DeviceGuard g0(phys_of(m, 0));
-    RT_HIP(hipEventRecord(m->ev_out, m->stream[0]));   // the caller's later work waits for it
-    RT_HIP(hipStreamWaitEvent(st, m->ev_out, 0));
-    return RT_OK;
+    return frame_end(m, st);
 }
 
 int rt_multi_adaptive_device_info(const rt_multi* m, uint32_t device, rt_adaptive_info* out) {
@@ -1224,19 +1140,7 @@ int rt_render(const Sphere* spheres, uint32_t sphere_count, const RenderCallInfo
         RT_HIP(hipStreamSynchronize(m->stream[0]));
         RT_HIP(hipMemcpy(accum, dacc, size_t(W) * H * 16, hipMemcpyDeviceToHost));
         RT_HIP(hipMemcpy(out, dout, size_t(W) * H * 4, hipMemcpyDeviceToHost));
-        if (stats) {
-            std::memset(stats, 0, sizeof(*stats));
-            for (Launch& l : m->launches) {
-                if (l.rows.empty()) continue;
-                rt_stats s;
-                if (int rc = rt_get_stats(l.ctx, &s)) return rc;
-                stats->segments += s.segments;
-                stats->samples += s.samples;
-                stats->box_tests += s.box_tests;
-                stats->sphere_tests += s.sphere_tests;
-            }
-        }
-        return RT_OK;
+        return stats ? rt_multi_stats(m, stats) : RT_OK;
     };
     int rc;
     try {

@@ -59,6 +59,65 @@ Parts row_parts(uint32_t n, uint32_t H, const uint32_t* rows, const uint32_t* co
     return at == H ? parts : Parts{};
 }
 
+namespace {
+
+// A frame plan under construction: the parts of a partition and what both frame kinds append.
+struct Builder {
+    FramePlan p;
+    uint32_t W, np;
+    bool whole = false, remote = false;   // a live `whole` part / a live part off device 0
+
+    Builder(uint32_t W_, uint32_t H, Parts&& parts) : W(W_) {
+        for (auto& pr : parts) {
+            PlanPart q;
+            q.dev = pr.first;
+            q.rows = std::move(pr.second);
+            q.whole = q.dev == 0 && q.rows.size() == H;
+            for (uint32_t y = 0; q.whole && y < H; y++) q.whole = q.rows[y] == y;
+            p.parts.push_back(std::move(q));
+        }
+        np = uint32_t(p.parts.size());
+        for (uint32_t i = 0; i < np; i++) {
+            whole |= live(i) && p.parts[i].whole;
+            remote |= live(i) && p.parts[i].dev != 0;
+        }
+    }
+    bool live(uint32_t i) const { return !p.parts[i].rows.empty(); }
+    uint64_t floats(uint32_t i) const { return uint64_t(p.parts[i].rows.size()) * W * 4u; }
+    uint64_t words(uint32_t i) const {   // the part's per-tile count table
+        return uint64_t((W + kStrip - 1) / kStrip) * ((p.parts[i].rows.size() + kStrip - 1) / kStrip);
+    }
+    void add(uint32_t op, uint32_t dev, uint32_t peer, uint32_t part, uint32_t flags, uint64_t count) {
+        p.steps.push_back(PlanStep{op, dev, peer, part, flags, count});
+    }
+    // every live part: `op` on its device (a render; kDirect for a whole part) or on device 0
+    void each_live(uint32_t op, bool on_part_dev) {
+        for (uint32_t i = 0; i < np; i++) {
+            if (!live(i)) continue;
+            const uint32_t d = on_part_dev ? p.parts[i].dev : 0u;
+            add(op, d, d, i, on_part_dev && p.parts[i].whole ? kDirect : 0u, on_part_dev ? 0u : floats(i));
+        }
+    }
+    // one group moving every remote part's band between its device and device 0 (each send beside
+    // its receive), with its count table when `counts`; nothing when no part is remote
+    void group(bool to_root, bool counts) {
+        if (!remote) return;
+        add(OP_GROUP_START, 0, 0, 0, 0, 0);
+        for (uint32_t i = 0; i < np; i++) {
+            if (!live(i) || p.parts[i].dev == 0) continue;
+            const uint32_t from = to_root ? p.parts[i].dev : 0u, to = to_root ? 0u : p.parts[i].dev;
+            add(OP_SEND, from, to, i, 0, floats(i));
+            add(OP_RECV, to, from, i, 0, floats(i));
+            if (!counts) continue;
+            add(OP_SEND_COUNTS, from, to, i, 0, words(i));
+            add(OP_RECV_COUNTS, to, from, i, 0, words(i));
+        }
+        add(OP_GROUP_END, 0, 0, 0, 0, 0);
+    }
+};
+
+}  // namespace
+
 // accumulate: every part starts from its rows of the caller's accumulator (rt_render_device's
 // accumulate semantics for the whole image, at any device count): device 0 loads them into its
 // own bands and into the stages of the other devices' parts, and sends those in one group. Then
@@ -67,98 +126,53 @@ Parts row_parts(uint32_t n, uint32_t H, const uint32_t* rows, const uint32_t* co
 // through RCCL; a `whole` part renders into the caller's buffers and needs nothing else (the
 // one-device frame).
 FramePlan make_plan(uint32_t W, uint32_t H, Parts&& parts, bool accumulate) {
-    FramePlan p;
-    for (auto& pr : parts) {
-        PlanPart q;
-        q.dev = pr.first;
-        q.rows = std::move(pr.second);
-        q.whole = q.dev == 0 && q.rows.size() == H;
-        for (uint32_t y = 0; q.whole && y < H; y++) q.whole = q.rows[y] == y;
-        p.parts.push_back(std::move(q));
+    Builder b(W, H, std::move(parts));
+    if (accumulate && !b.whole) {
+        b.each_live(OP_LOAD_ROWS, false);
+        b.group(false, false);
     }
-    const uint32_t np = uint32_t(p.parts.size());
-    auto live = [&](uint32_t i) { return !p.parts[i].rows.empty(); };
-    auto floats = [&](uint32_t i) { return uint64_t(p.parts[i].rows.size()) * W * 4u; };
-    auto add = [&](uint32_t op, uint32_t dev, uint32_t peer, uint32_t part, uint32_t flags, uint64_t count) {
-        p.steps.push_back(PlanStep{op, dev, peer, part, flags, count});
-    };
-    bool whole = false, remote = false;
-    for (uint32_t i = 0; i < np; i++) {
-        whole |= live(i) && p.parts[i].whole;
-        remote |= live(i) && p.parts[i].dev != 0;
-    }
-    if (accumulate && !whole) {
-        for (uint32_t i = 0; i < np; i++)
-            if (live(i)) add(OP_LOAD_ROWS, 0, 0, i, 0, floats(i));
-        if (remote) {
-            add(OP_GROUP_START, 0, 0, 0, 0, 0);
-            for (uint32_t i = 0; i < np; i++) {
-                if (!live(i) || p.parts[i].dev == 0) continue;
-                add(OP_SEND, 0, p.parts[i].dev, i, 0, floats(i));
-                add(OP_RECV, p.parts[i].dev, 0, i, 0, floats(i));
-            }
-            add(OP_GROUP_END, 0, 0, 0, 0, 0);
-        }
-    }
-    for (uint32_t i = 0; i < np; i++)
-        if (live(i)) add(OP_RENDER, p.parts[i].dev, p.parts[i].dev, i, p.parts[i].whole ? kDirect : 0u, 0);
-    if (whole) return p;
-    if (remote) {
-        add(OP_GROUP_START, 0, 0, 0, 0, 0);
-        for (uint32_t i = 0; i < np; i++) {
-            if (!live(i) || p.parts[i].dev == 0) continue;
-            add(OP_SEND, p.parts[i].dev, 0, i, 0, floats(i));
-            add(OP_RECV, 0, p.parts[i].dev, i, 0, floats(i));
-        }
-        add(OP_GROUP_END, 0, 0, 0, 0, 0);
-    }
-    for (uint32_t i = 0; i < np; i++)
-        if (live(i)) add(OP_STORE_ROWS, 0, 0, i, 0, floats(i));
-    add(OP_RESOLVE, 0, 0, 0, 0, uint64_t(W) * H);
-    return p;
+    b.each_live(OP_RENDER, true);
+    if (b.whole) return std::move(b.p);
+    b.group(true, false);
+    b.each_live(OP_STORE_ROWS, false);
+    b.add(OP_RESOLVE, 0, 0, 0, 0, uint64_t(W) * H);
+    return std::move(b.p);
 }
 
 FramePlan make_adaptive_plan(uint32_t W, uint32_t H, Parts&& parts) {
-    FramePlan p;
-    for (auto& pr : parts) {
-        PlanPart q;
-        q.dev = pr.first;
-        q.rows = std::move(pr.second);
-        q.whole = q.dev == 0 && q.rows.size() == H;
-        for (uint32_t y = 0; q.whole && y < H; y++) q.whole = q.rows[y] == y;
-        p.parts.push_back(std::move(q));
-    }
-    const uint32_t np = uint32_t(p.parts.size());
-    auto live = [&](uint32_t i) { return !p.parts[i].rows.empty(); };
-    auto floats = [&](uint32_t i) { return uint64_t(p.parts[i].rows.size()) * W * 4u; };
-    auto words = [&](uint32_t i) {
-        return uint64_t((W + kStrip - 1) / kStrip) * ((p.parts[i].rows.size() + kStrip - 1) / kStrip);
-    };
-    auto add = [&](uint32_t op, uint32_t dev, uint32_t peer, uint32_t part, uint32_t flags, uint64_t count) {
-        p.steps.push_back(PlanStep{op, dev, peer, part, flags, count});
-    };
-    bool whole = false, remote = false;
-    for (uint32_t i = 0; i < np; i++) {
-        whole |= live(i) && p.parts[i].whole;
-        remote |= live(i) && p.parts[i].dev != 0;
-    }
-    for (uint32_t i = 0; i < np; i++)
-        if (live(i)) add(OP_RENDER_ADAPTIVE, p.parts[i].dev, p.parts[i].dev, i, p.parts[i].whole ? kDirect : 0u, 0);
-    if (whole) return p;
-    if (remote) {
-        add(OP_GROUP_START, 0, 0, 0, 0, 0);
-        for (uint32_t i = 0; i < np; i++) {
-            if (!live(i) || p.parts[i].dev == 0) continue;
-            add(OP_SEND, p.parts[i].dev, 0, i, 0, floats(i));
-            add(OP_RECV, 0, p.parts[i].dev, i, 0, floats(i));
-            add(OP_SEND_COUNTS, p.parts[i].dev, 0, i, 0, words(i));
-            add(OP_RECV_COUNTS, 0, p.parts[i].dev, i, 0, words(i));
+    Builder b(W, H, std::move(parts));
+    b.each_live(OP_RENDER_ADAPTIVE, true);
+    if (b.whole) return std::move(b.p);
+    b.group(true, true);
+    b.each_live(OP_STORE_TILES, false);
+    return std::move(b.p);
+}
+
+bool pair_group(const PlanStep* group, size_t n, std::vector<std::pair<size_t, size_t>>& pairs) {
+    pairs.clear();
+    auto send_of = [](uint32_t op) { return op == OP_RECV ? OP_SEND : op == OP_RECV_COUNTS ? OP_SEND_COUNTS : 0u; };
+    std::vector<uint8_t> taken(n, 0);
+    size_t sends = 0;
+    for (size_t r = 0; r < n; r++) {
+        const uint32_t want = send_of(group[r].op);
+        if (!want) {
+            if (group[r].op != OP_SEND && group[r].op != OP_SEND_COUNTS) return false;   // no transfer
+            sends++;
+            continue;
         }
-        add(OP_GROUP_END, 0, 0, 0, 0, 0);
+        size_t s = n;
+        for (size_t c = 0; c < n; c++) {
+            if (group[c].op != want || group[c].dev != group[r].peer || group[c].peer != group[r].dev ||
+                group[c].part != group[r].part)
+                continue;
+            if (s != n) return false;   // two sends for one receive
+            s = c;
+        }
+        if (s == n || taken[s] || group[s].count != group[r].count) return false;
+        taken[s] = 1;
+        pairs.emplace_back(r, s);
     }
-    for (uint32_t i = 0; i < np; i++)
-        if (live(i)) add(OP_STORE_TILES, 0, 0, i, 0, floats(i));
-    return p;
+    return pairs.size() == sends;   // no send left over
 }
 
 std::vector<uint32_t> serialize(const FramePlan& p) {

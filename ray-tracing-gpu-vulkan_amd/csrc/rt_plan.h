@@ -11,6 +11,7 @@
 // frame rescales to the device times (no teardown: only rows maps change).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <utility>
 #include <vector>
@@ -90,6 +91,14 @@ FramePlan make_plan(uint32_t W, uint32_t H, Parts&& parts, bool accumulate);
 // words) to device 0; one fused store per part writes accumulator, rgba8 and counts in place (no
 // whole-image resolve). A `whole` part renders into the caller's buffers and needs nothing else.
 FramePlan make_adaptive_plan(uint32_t W, uint32_t H, Parts&& parts);
+
+// The transfers of one group (the `n` steps between its OP_GROUP_START and OP_GROUP_END), as the
+// logical transport of rt_multi executes them: every receive with its send, the send of the same
+// kind (OP_SEND for OP_RECV, OP_SEND_COUNTS for OP_RECV_COUNTS) and part with dev / peer mirrored
+// and an equal count. `pairs` receives {receive, send} indices into `group`, in receive order.
+// False when a receive has no send or more than one, a count differs, a send is left over or a
+// step is no transfer.
+bool pair_group(const PlanStep* group, size_t n, std::vector<std::pair<size_t, size_t>>& pairs);
 
 // Flat form (rt_debug_multi_plan): {n_parts, n_steps}, per part {dev, whole, n_rows, rows...},
 // per step {op, dev, peer, part, flags, count low, count high}.

@@ -10,7 +10,9 @@
 //   * the grid layout of the device build (grid_layout, config 5's bounds);
 //   * the multi-device partition, balancer and frame plan (csrc/rt_plan.cpp): every device count
 //     1-9 over the image heights of the configs and small odd ones, random partitions, random
-//     device times and row weights, malformed inputs;
+//     device times and row weights, malformed inputs; the tile-row partition and plan of adaptive
+//     frames; every group of every plan through the pairing the logical transport executes
+//     (pair_group), and mutilated groups refused;
 //   * the single-device launch plan and the row weights (csrc/rt_launch.cpp): scenes, bands, sample
 //     counts, streams, forms and tuning values of tests/test_launch_plan.py plus the extremes (one
 //     CU, 1x1 and 65535x65535 bands, 0 samples, no spheres, tuning values up to 2^32), every plan
@@ -316,6 +318,59 @@ void check_tree(const std::vector<Sphere>& s, bool sah) {
     }
 }
 
+// The groups of a plan under the pairing the logical transport executes (rt_plan.h pair_group):
+// every receive pairs with exactly one send of equal count and no send is left over; a group with
+// a send removed or a count altered is refused. No transfer stands outside a group.
+void check_groups(const rt::plan::FramePlan& p) {
+    using namespace rt::plan;
+    auto is_send = [](const PlanStep& s) { return s.op == OP_SEND || s.op == OP_SEND_COUNTS; };
+    auto is_recv = [](const PlanStep& s) { return s.op == OP_RECV || s.op == OP_RECV_COUNTS; };
+    std::vector<std::pair<size_t, size_t>> pairs;
+    bool open = false;
+    std::vector<PlanStep> group;
+    for (const PlanStep& s : p.steps) {
+        if (s.op == OP_GROUP_START) {
+            CHECK(!open);
+            open = true;
+            group.clear();
+        } else if (s.op == OP_GROUP_END) {
+            CHECK(open && !group.empty());
+            open = false;
+            CHECK(pair_group(group.data(), group.size(), pairs));
+            CHECK(2 * pairs.size() == group.size());
+            std::vector<int> used(group.size(), 0);
+            for (const auto& pr : pairs) {
+                CHECK(pr.first < group.size() && pr.second < group.size());
+                const PlanStep &r = group[pr.first], &t = group[pr.second];
+                CHECK(is_recv(r) && is_send(t) && (r.op == OP_RECV) == (t.op == OP_SEND));
+                CHECK(r.count == t.count && r.part == t.part && r.dev == t.peer && r.peer == t.dev);
+                used[pr.first]++;
+                used[pr.second]++;
+            }
+            for (int u : used) CHECK(u == 1);
+            const size_t a_send = pairs[0].second;
+            for (size_t k = 0; k < group.size(); k++) {
+                std::vector<PlanStep> cut = group;   // one step removed: a receive without its send, or a send left over
+                cut.erase(cut.begin() + std::ptrdiff_t(k));
+                CHECK(!pair_group(cut.data(), cut.size(), pairs));
+                std::vector<PlanStep> off = group;   // one count altered
+                off[k].count += 1;
+                CHECK(!pair_group(off.data(), off.size(), pairs));
+            }
+            std::vector<PlanStep> twice = group;     // a second send for one receive
+            twice.push_back(group[a_send]);
+            CHECK(!pair_group(twice.data(), twice.size(), pairs));
+            CHECK(pair_group(group.data(), 0, pairs) && pairs.empty());
+        } else if (open) {
+            CHECK(is_send(s) || is_recv(s));
+            group.push_back(s);
+        } else {
+            CHECK(!is_send(s) && !is_recv(s));
+        }
+    }
+    CHECK(!open);
+}
+
 void check_plans() {
     using namespace rt::plan;
     std::mt19937 g(2024);
@@ -340,6 +395,19 @@ void check_plans() {
                 const FramePlan p = make_plan(1920, H, std::move(cp), acc != 0);
                 const std::vector<uint32_t> v = serialize(p);
                 CHECK(v.size() >= 2 && v[0] == p.parts.size() && v[1] == p.steps.size());
+                check_groups(p);
+            }
+            {   // adaptive frames: whole tile rows, every row once, and their plan's groups
+                Parts tp = tile_row_parts(n, H);
+                CHECK(tp.size() == std::min(n, (H + kStrip - 1) / kStrip));
+                std::vector<int> seen_t(H, 0);
+                for (auto& p : tp)
+                    for (uint32_t y : p.second) {
+                        CHECK(y < H);
+                        seen_t[y]++;
+                    }
+                for (uint32_t y = 0; y < H; y++) CHECK(seen_t[y] == 1);
+                check_groups(make_adaptive_plan(1920, H, std::move(tp)));
             }
             // balancing: random row costs, random device times and weights, a few rounds
             std::vector<double> cost(H, 0.0);
