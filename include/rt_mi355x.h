@@ -277,6 +277,30 @@ int rt_sample_map_set_from_adaptive(rt_sample_map* map, uint32_t quantum, void* 
 /* The info of the last successful set call (zeros but `tiles` before one). */
 int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out);
 /*
+ * The schedule of a map's frames. RT_SAMPLE_MAP_LEVELS (the default) is the plan above. Under
+ * RT_SAMPLE_MAP_ONE_LAUNCH the whole frame is one trace launch of a block table, whatever the number
+ * of distinct counts (no limit of 64): the tiles in the same order, those of count 0 dropped, a tile
+ * of count n split into k = ceil(n / U) chunks, chunk c = samples [c n / k, (c + 1) n / k); the
+ * table lists the chunks tile by tile, one 16-byte entry {tile, s0, s1, 0} per block of 64 units, so
+ * the high-count tiles' ~U-sample units lead and the low-count tiles' single short units are the
+ * tail. The image is the same bit for bit under either schedule.
+ *   unit_samples   U: 0 = automatic, max(clamp(max_count / 32, 32, 128), ceil(sum of 64 n[t] /
+ *                  (393 216 lanes x 128))), doubled until 64 x blocks < 2^31; else within [1, 2^19];
+ *                  must be 0 with RT_SAMPLE_MAP_LEVELS.
+ * The call takes effect at the next set call; the plan the map holds stays until then.
+ * RT_ERR_INVALID_ARGUMENT: an unknown schedule, unit_samples above 2^19 or given with LEVELS. A set
+ * call whose block table with the caller's U has 2^25 blocks or more is refused (the message names
+ * the smallest U that fits) and leaves the map as it was. Under ONE_LAUNCH rt_sample_map_info.levels
+ * holds the distinct non-zero counts (it may exceed 64) and tile_launches the non-zero tiles.
+ */
+#define RT_SAMPLE_MAP_LEVELS 0u
+#define RT_SAMPLE_MAP_ONE_LAUNCH 1u
+int rt_sample_map_set_schedule(rt_sample_map* map, uint32_t schedule, uint32_t unit_samples);
+/* The schedule, U and block count of the plan the map holds (LEVELS, 0, 0 before a set call and for
+ * a level plan); every output may be NULL. */
+int rt_sample_map_get_schedule(const rt_sample_map* map, uint32_t* schedule, uint32_t* unit_samples_used,
+                               uint64_t* n_blocks);
+/*
  * One sample-map frame of a band, asynchronous on `stream`: arguments as rt_render_adaptive_device.
  * The call contains no host wait, no event synchronisation and no blocking copy; a map may be
  * rendered any number of times, on any stream of its context, between plain and adaptive calls.
@@ -287,6 +311,7 @@ int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out);
  * accumulate, a band size other than the map's, the cap, a map never set, a map of another context,
  * an adaptive frame open on ctx. RT_ERR_NO_SCENE before rt_set_scene.
  * Each level's launch counts as one launch for rt_launch_ms; rt_get_stats reports the last launch.
+ * A one-launch map's frame is one launch for both: that launch is the whole frame.
  * Map frames neither read nor update the tile order of rt_render_device launches, record no row
  * weights and leave the count table of the last adaptive frame in place.
  */
@@ -300,6 +325,14 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
 int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum,
                        uint32_t* order, uint32_t* levels, uint32_t* level_tiles, uint32_t* n_levels,
                        uint32_t* quantised);
+/* The block table of a host table under RT_SAMPLE_MAP_ONE_LAUNCH (host only; what the set calls
+ * compute): blocks_out holds 4 words {tile, s0, s1, 0} per block, `capacity` blocks; every output may
+ * be NULL (blocks_out NULL: a size query). Refusals as rt_sample_map_plan's but the level limit, plus
+ * unit_samples above 2^19, a table of 2^25 blocks or more, a capacity below the table; nothing is
+ * written then. */
+int rt_sample_map_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum,
+                             uint32_t unit_samples, uint32_t* blocks_out, uint64_t capacity,
+                             uint64_t* n_blocks, uint32_t* unit_samples_used);
 /* Statistics of the last completed rt_render_device (synchronises ctx's last stream). */
 int rt_get_stats(rt_context* ctx, rt_stats* out);
 /* Trace-kernel duration (ms, HIP events on the launch stream) of ctx's launch `back` launches

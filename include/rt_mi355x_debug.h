@@ -100,9 +100,14 @@ int rt_debug_tile_cost(rt_context* ctx, uint32_t* out, uint64_t capacity, uint64
 /* Diagnostic (tests): what the device holds of a sample map after its last set call, copied back:
  * order and quantised (the map's tile count of words each, either may be NULL) from device memory,
  * levels and level_tiles (RT_SAMPLE_MAP_MAX_LEVELS words each, either may be NULL) from the host
- * plan the launches are sized by. Waits for the frames queued on the map. */
+ * plan the launches are sized by (of a one-launch plan with more levels, the lowest
+ * RT_SAMPLE_MAP_MAX_LEVELS). Waits for the frames queued on the map. */
 int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* levels, uint32_t* level_tiles,
                         uint32_t* quantised);
+/* Diagnostic (tests): the block table the device holds of a map set under RT_SAMPLE_MAP_ONE_LAUNCH,
+ * copied back: 4 words {tile, s0, s1, 0} per block into `out` (`capacity` blocks; NULL: a size
+ * query), *n = blocks (0 for a level plan). Waits for the frames queued on the map. */
+int rt_debug_sample_map_blocks(const rt_sample_map* map, uint32_t* out, uint64_t capacity, uint64_t* n);
 /* The rt_sample_map_info a set call would report for a host table over a band (host only). */
 int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, uint32_t band_height,
                              uint32_t quantum, rt_sample_map_info* out);

@@ -221,6 +221,11 @@ struct rt_sample_map {
     bool set = false;
     rt::sample_map::Plan plan;
     rt_sample_map_info info{};
+    // the schedule the next set call plans by (rt_sample_map_set_schedule), and the one the held plan has
+    uint32_t next_schedule = RT_SAMPLE_MAP_LEVELS, next_unit = 0;
+    uint32_t schedule = RT_SAMPLE_MAP_LEVELS, unit_samples = 0;
+    rt::BlockEntry* blocks = nullptr;    // device: the block table of a one-launch plan (n_blocks entries)
+    uint64_t n_blocks = 0, cap_blocks = 0;
     hipEvent_t ev_read = nullptr;
     mutable bool read_pending = false;   // ev_read has been recorded since the last set call
 };
@@ -1368,8 +1373,9 @@ AdaptiveBuffers adaptive_buffers(rt_context* ctx) {
 
 // The set calls of a sample map, the one synchronous step: waits for the frames
 // that read the map, brings the count table `d_counts` (written by earlier work on `st`) to the
-// host, plans it there and uploads the order and the quantised table. A refusal leaves the map as
-// it was.
+// host, plans it there and uploads the order and the quantised table, under the one-launch schedule
+// the block table too (into a buffer of its own, grown before anything of the map changes). A
+// refusal leaves the map as it was.
 int sample_map_set(rt_sample_map* map, const uint32_t* d_counts, uint32_t quantum, hipStream_t st,
                    rt_sample_map_info* info) {
     const size_t n = map->n_tiles;
@@ -1378,17 +1384,44 @@ int sample_map_set(rt_sample_map* map, const uint32_t* d_counts, uint32_t quantu
     RT_HIP(hipMemcpyAsync(map->stage, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RT_HIP(hipStreamSynchronize(st));
     rt::sample_map::Plan plan;
+    rt::sample_map::BlockPlan bp;
     rt_sample_map_info fresh{};
     std::string err;
-    if (int rc = rt::sample_map::make_plan(map->stage, map->n_tiles, quantum, plan, &err)) return fail(rc, err);
+    const bool one = map->next_schedule == RT_SAMPLE_MAP_ONE_LAUNCH;
+    if (one) {
+        if (int rc = rt::sample_map::make_block_plan(map->stage, map->n_tiles, quantum, map->next_unit, bp, &err))
+            return fail(rc, err);
+        plan = std::move(bp.plan);
+    } else if (int rc = rt::sample_map::make_plan(map->stage, map->n_tiles, quantum, plan, &err)) {
+        return fail(rc, err);
+    }
     if (int rc = rt::sample_map::totals(plan, map->band_w, map->band_h, &fresh, &err)) return fail(rc, err);
+    if (one) fresh.tile_launches = bp.live_tiles;   // every non-zero tile is launched once
+    rt::BlockEntry* grown = nullptr;
+    if (one && bp.blocks.size() > map->cap_blocks) {
+        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), bp.blocks.size() * sizeof(rt::BlockEntry)); e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE,
+                        std::string("rt_sample_map block table: ") + hipGetErrorString(e));
+    }
     std::copy(plan.order.begin(), plan.order.end(), map->stage);
     std::copy(plan.quantised.begin(), plan.quantised.end(), map->stage + n);
     map->set = false;   // until the upload has landed
+    if (grown) {   // (no frame reads the old table: ev_read was waited for above)
+        (void)hipFree(map->blocks);
+        map->blocks = grown;
+        map->cap_blocks = bp.blocks.size();
+    }
+    map->n_blocks = 0;
     RT_HIP(hipMemcpyAsync(map->table, map->stage, 2u * n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (one && !bp.blocks.empty())
+        RT_HIP(hipMemcpyAsync(map->blocks, bp.blocks.data(), bp.blocks.size() * sizeof(rt::BlockEntry),
+                              hipMemcpyHostToDevice, st));
     RT_HIP(hipStreamSynchronize(st));   // frames on any stream of the context may follow
     map->plan = std::move(plan);
     map->info = fresh;
+    map->schedule = map->next_schedule;
+    map->unit_samples = one ? bp.unit_samples : 0u;
+    map->n_blocks = one ? bp.blocks.size() : 0u;
     map->set = true;
     if (info) *info = fresh;
     return RT_OK;
@@ -1768,6 +1801,7 @@ int rt_sample_map_destroy(rt_sample_map* map) {
     rt::DeviceGuard g(map->ctx->device);
     if (map->read_pending) (void)hipEventSynchronize(map->ev_read);   // the frames that read it
     (void)hipFree(map->table);
+    (void)hipFree(map->blocks);
     (void)hipHostFree(map->stage);
     (void)hipEventDestroy(map->ev_read);
     delete map;
@@ -1806,6 +1840,53 @@ int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out) {
     return RT_OK;
 }
 
+int rt_sample_map_set_schedule(rt_sample_map* map, uint32_t schedule, uint32_t unit_samples) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    if (schedule != RT_SAMPLE_MAP_LEVELS && schedule != RT_SAMPLE_MAP_ONE_LAUNCH)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_schedule: unknown schedule " + std::to_string(schedule));
+    if (schedule == RT_SAMPLE_MAP_LEVELS && unit_samples != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_schedule: unit_samples must be 0 with RT_SAMPLE_MAP_LEVELS");
+    if (unit_samples > rt::sample_map::kMaxUnit)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "rt_sample_map_set_schedule: unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
+    map->next_schedule = schedule;
+    map->next_unit = unit_samples;
+    return RT_OK;
+}
+
+int rt_sample_map_get_schedule(const rt_sample_map* map, uint32_t* schedule, uint32_t* unit_samples_used,
+                               uint64_t* n_blocks) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    if (schedule) *schedule = map->schedule;
+    if (unit_samples_used) *unit_samples_used = map->unit_samples;
+    if (n_blocks) *n_blocks = map->n_blocks;
+    return RT_OK;
+}
+
+int rt_sample_map_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t unit_samples,
+                             uint32_t* blocks_out, uint64_t capacity, uint64_t* n_blocks, uint32_t* unit_samples_used) {
+    std::string err;
+    if (int rc = rt::sample_map::block_plan_arrays(tile_counts, n_tiles, quantum, unit_samples, blocks_out, capacity,
+                                                   n_blocks, unit_samples_used, &err))
+        return fail(rc, err);
+    return RT_OK;
+}
+
+int rt_debug_sample_map_blocks(const rt_sample_map* map, uint32_t* out, uint64_t capacity, uint64_t* n) {
+    if (!map || !n) return fail(RT_ERR_INVALID_ARGUMENT, "map or n is NULL");
+    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: the map was never set");
+    if (out && capacity < map->n_blocks)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: capacity is below the table's " +
+                                                 std::to_string(map->n_blocks) + " blocks");
+    rt::DeviceGuard g(map->ctx->device);
+    if (out && map->n_blocks) {
+        if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+        RT_HIP(hipMemcpy(out, map->blocks, map->n_blocks * sizeof(rt::BlockEntry), hipMemcpyDeviceToHost));
+    }
+    *n = map->n_blocks;
+    return RT_OK;
+}
+
 int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t* order,
                        uint32_t* levels, uint32_t* level_tiles, uint32_t* n_levels, uint32_t* quantised) {
     std::string err;
@@ -1836,13 +1917,16 @@ int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* lev
     const size_t n = map->n_tiles;
     if (order) RT_HIP(hipMemcpy(order, map->table, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (quantised) RT_HIP(hipMemcpy(quantised, map->table + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (levels) std::copy(map->plan.levels.begin(), map->plan.levels.end(), levels);
-    if (level_tiles) std::copy(map->plan.level_tiles.begin(), map->plan.level_tiles.end(), level_tiles);
+    // (a one-launch plan may hold more levels than the arrays: the lowest RT_SAMPLE_MAP_MAX_LEVELS)
+    const size_t j = std::min<size_t>(map->plan.levels.size(), RT_SAMPLE_MAP_MAX_LEVELS);
+    if (levels) std::copy_n(map->plan.levels.begin(), j, levels);
+    if (level_tiles) std::copy_n(map->plan.level_tiles.begin(), j, level_tiles);
     return RT_OK;
 }
 
-// The whole frame is queued: one trace launch per level on the nested prefixes of the map's order,
-// then the resolve with the map as per-tile divisors. No host wait, no event synchronisation and no
+// The whole frame is queued: one trace launch per level on the nested prefixes of the map's order
+// (a one-launch plan: one launch of its block table), then the resolve with the map as per-tile
+// divisors. No host wait, no event synchronisation and no
 // blocking copy below (the buffers' first allocation and growth in adaptive_reserve aside).
 int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
                                 uint32_t band_height, float* accum, uint8_t* out, uint32_t* sample_count,
@@ -1888,8 +1972,22 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
     P.head_tiles = 0u;
     // (after a failure between the first launch and the resolve the planes hold partial sums:
     // abort_on_planes)
+    if (map->schedule == RT_SAMPLE_MAP_ONE_LAUNCH) {
+        if (map->n_blocks) {   // (an all-zero map: the resolve alone)
+            P.block_tab = map->blocks;
+            P.tile_order = nullptr;
+            P.chunks = P.head_chunks = 1u;
+            P.n_units = uint32_t(map->n_blocks * 64u);   // < 2^31 (rt_sample_map.h kMaxBlocks)
+            S.plan.lpt = 1u;
+            S.plan.chunks = S.plan.head_chunks = 1u;
+            S.plan.head_tiles = 0u;
+            S.plan.n_units = P.n_units;
+            rt::launch::hand_out_units(S.in, S.plan, true);
+            if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
+        }
+    }
     uint32_t prev = 0;
-    for (size_t j = 0; j < map->plan.levels.size(); j++) {   // samples [L_{j-1}, L_j) on the first c_j tiles
+    for (size_t j = 0; map->schedule == RT_SAMPLE_MAP_LEVELS && j < map->plan.levels.size(); j++) {   // samples [L_{j-1}, L_j) on the first c_j tiles
         const uint32_t level = map->plan.levels[j];
         if (int rc = launch_tile_prefix(ctx, S, level - prev, o.sample_base + prev, map->plan.level_tiles[j], true, st))
             return abort_on_planes(ctx, st, rc);

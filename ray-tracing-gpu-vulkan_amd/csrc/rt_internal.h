@@ -178,6 +178,12 @@ struct Counters {
                                         // lanes only [1]; primary lanes' summed work [2], count [3]
 };
 
+// One block of a table launch (TraceParams::block_tab): samples [s0, s1) of the 64 pixels of 8x8
+// tile `tile`. 16 bytes, read by the kernels as one uint4 (rt_sample_map.h Block on the host).
+struct alignas(16) BlockEntry {
+    uint32_t tile, s0, s1, zero;
+};
+
 // Kernel launch parameters (passed by value as the kernel argument).
 //
 // Work units: unit u = (8x8 tile, sample chunk, pixel of the tile). Block b = u / 64 covers one
@@ -185,6 +191,10 @@ struct Counters {
 // of the head ranks, then likewise over the remaining blocks with n = chunks; the tile is
 // tile_order[rank] (LPT hand-out) or the rank itself. Chunk c of n runs samples
 // [c * spp / n, (c + 1) * spp / n). STREAM launches have one chunk.
+// Table form (HASH only, block_tab != null; launch_trace then picks the kernels' TAB instantiation):
+// block b is block_tab[b], whatever tile and sample range the host wrote there; n_units = 64 *
+// entries, and tile_order, chunks, head_tiles and head_chunks are unused. The hand-out itself
+// (n_block_units, first_blocks, the one-by-one reserve) is the same.
 struct TraceParams {
     // Camera / viewport (shader.rgen:92-115), computed once per launch on the host.
     float lf[3], hor[3], ver[3], ulc[3], cup[3], crt[3];
@@ -248,6 +258,8 @@ struct TraceParams {
     const float* big_tab;          // the big spheres as kBigMax records {cx, cy, cz, r} (padded to a
                                    // multiple of 4 by repeating the last) + kBigMax ids, filled per
                                    // launch (rt_big_table_kernel), read through the scalar cache
+    const BlockEntry* block_tab;   // optional: the table form (null: the uniform hand-out above). Last, so
+                                   // that every other parameter keeps its place in the kernel argument
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,

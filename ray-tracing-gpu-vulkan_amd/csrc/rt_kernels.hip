@@ -410,6 +410,13 @@ __device__ __forceinline__ float4 load_now4(const float4* p) {
     __builtin_amdgcn_s_waitcnt(0x0F70);
     return make_float4(v.x, v.y, v.z, v.w);
 }
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+typedef const volatile __attribute__((address_space(1))) u4v* GlobalVU4;
+__device__ __forceinline__ rt::BlockEntry load_now_block(const rt::BlockEntry* p) {
+    const u4v v = *(GlobalVU4)p;
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    return rt::BlockEntry{v.x, v.y, v.z, v.w};
+}
 
 // RT_RNG_SAMPLE_HASH: LCG start of sample s of a pixel. One multiply-add
 // spreads consecutive sample indices (golden ratio), then the "lowbias32" integer finaliser
@@ -553,6 +560,21 @@ __device__ __forceinline__ uint32_t block_tile(const rt::TraceParams& P, uint32_
     return P.tile_order ? load_now(P.tile_order + rank) : rank;
 }
 
+// Table form (TAB kernels: HASH launches with a block table, rt_internal.h): block b (wave-uniform)
+// is its table entry, one 16-byte load waited for at once where block_tile loads; the values are
+// wave-uniform and go to SGPRs. Once per 64 units, outside the segment loop. The table form is a
+// template parameter of the kernels, not a branch on P.block_tab: the branch cost the uniform
+// launches 0.4 % of the headline.
+__device__ __forceinline__ void take_block_tab(const rt::TraceParams& P, uint32_t lane, WaveBlock& blk, uint32_t b) {
+    const rt::BlockEntry e = load_now_block(P.block_tab + b);
+    blk.next = b * 64u;
+    blk.end = blk.next + 64u;
+    blk.tile = __builtin_amdgcn_readfirstlane(e.tile);
+    blk.s0 = __builtin_amdgcn_readfirstlane(e.s0);
+    blk.s1 = __builtin_amdgcn_readfirstlane(e.s1);
+    blk.seed = tile_pixel_seed(P, blk.tile, lane);
+}
+
 template <int MODE>
 __device__ __forceinline__ void begin_unit(const rt::TraceParams& P, Path& ps, uint32_t lx, uint32_t ly,
                                            uint32_t seed, uint32_t s0, uint32_t s1) {
@@ -606,7 +628,7 @@ __device__ __forceinline__ void steal_tail(const rt::TraceParams& P, uint32_t la
     }
 }
 
-template <int MODE, bool COUNT>
+template <int MODE, bool COUNT, bool TAB = false>
 __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, uint32_t& st, Path& ps,
                                        WaveBlock& blk, Stamps& stamps) {
     if (MODE == rt::MODE_HASH && blk.done) steal_tail<COUNT>(P, lane, st, ps);   // wave-uniform condition
@@ -633,7 +655,8 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
             if (nb >= P.n_block_units) blk.dry = true;
         }
         if (!blk.dry) {
-            take_block(P, lane, blk, nb >> 6, block_tile(P, nb >> 6));
+            if (TAB) take_block_tab(P, lane, blk, nb >> 6);
+            else take_block(P, lane, blk, nb >> 6, block_tile(P, nb >> 6));
             const uint32_t sn = __shfl(blk.seed, int((rank - avail) & 63u));
             if (rank >= avail) { u = nb + (rank - avail); t = blk.tile; seed = sn; s0 = blk.s0; s1 = blk.s1; }
             blk.next = nb + rest;
@@ -652,10 +675,17 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
     if (per_lane) {
         if (u >= P.n_units) { st = ST_RETIRED; return; }
         const uint32_t b = u >> 6;
-        const BlockChunk bc = block_chunk(P, b);
-        t = P.tile_order ? load_now(P.tile_order + bc.rank) : bc.rank;
-        s0 = chunk_begin(P, bc.c, bc.n);
-        s1 = chunk_begin(P, bc.c + 1u, bc.n);
+        if (TAB) {   // entry u >> 6, per lane
+            const rt::BlockEntry e = load_now_block(P.block_tab + b);
+            t = e.tile;
+            s0 = e.s0;
+            s1 = e.s1;
+        } else {
+            const BlockChunk bc = block_chunk(P, b);
+            t = P.tile_order ? load_now(P.tile_order + bc.rank) : bc.rank;
+            s0 = chunk_begin(P, bc.c, bc.n);
+            s1 = chunk_begin(P, bc.c + 1u, bc.n);
+        }
     }
     const uint32_t w = u & 63u;
     const uint32_t lx = (t % P.tiles_x) * 8u + (w & 7u);
@@ -670,10 +700,12 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
 // them): 16 Ki waves asking one address at once would queue for ~0.1 ms. Block ranks are dealt
 // across blocks of the grid first (rank = wave-in-block * grid + block), so the longest chains of
 // the LPT order start on different CUs (and XCDs) instead of sharing block 0's SIMDs.
+template <bool TAB = false>
 __device__ __forceinline__ void first_block(const rt::TraceParams& P, uint32_t lane, WaveBlock& blk) {
     const uint32_t wid = (threadIdx.x >> 6) * gridDim.x + blockIdx.x;
     if (wid < P.first_blocks) {
-        take_block(P, lane, blk, wid, block_tile(P, wid));
+        if (TAB) take_block_tab(P, lane, blk, wid);
+        else take_block(P, lane, blk, wid, block_tile(P, wid));
         if (wid < P.isolate_blocks) blk.dry = blk.done = true;   // no work beyond its first block
     }
 }
@@ -955,7 +987,7 @@ constexpr uint32_t kTraceBlock = RT_TRACE_BLOCK;   // one block per CU shares on
 // Brute-force kernel: one segment per loop iteration for every lane (the sphere loop is
 // wave-uniform, so there is no traversal divergence to manage).
 // ---------------------------------------------------------------------------------------------
-template <bool COUNT, int MODE>
+template <bool COUNT, int MODE, bool TAB = false>
 __global__ __launch_bounds__(kBruteBlock, RT_BRUTE_WAVES_PER_SIMD) void rt_trace_brute_kernel(const rt::TraceParams P) {
     const uint32_t lane = lane_id();
     const Camera cam = load_camera(P);
@@ -964,10 +996,10 @@ __global__ __launch_bounds__(kBruteBlock, RT_BRUTE_WAVES_PER_SIMD) void rt_trace
     V3 o = v3(0, 0, 0), d = v3(0, 0, 1);
     uint32_t n_seg = 0, n_smp = 0, n_sph = 0;
     WaveBlock blk;
-    first_block(P, lane, blk);
+    first_block<TAB>(P, lane, blk);
     STAMP_DECL;
     for (;;) {
-        refill<MODE, COUNT>(P, lane, st, ps, blk, stamps);
+        refill<MODE, COUNT, TAB>(P, lane, st, ps, blk, stamps);
         if (st == ST_NEED_SAMPLE) {
             if (start_sample<MODE, false>(P, cam, ps, o, d)) { st = ST_TRACING; n_smp++; }
             else st = ST_NEED_UNIT;
@@ -1777,7 +1809,7 @@ __device__ __forceinline__ void walk(const rt::TraceParams& P, const float4* __r
 // longest walk ends. Stamp slots: 0 loop head, 4 sample start, 5 refill, 6 block fetch, 1 ray
 // setup (big spheres), 2 LBVH walk, 3 shading, 7 other.
 // ---------------------------------------------------------------------------------------------
-template <bool COUNT, int LAYOUT, int MODE, bool REC = false, bool FLAT = false>
+template <bool COUNT, int LAYOUT, int MODE, bool REC = false, bool FLAT = false, bool TAB = false>
 __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4* __restrict__ nodes4,
                                           const float4* __restrict__ leaf4,
                                           const uint32_t* __restrict__ leaf_ids,
@@ -1805,13 +1837,13 @@ __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4
     unsigned long long wave_iters = 0;
     bool saw_dry = false;
     WaveBlock blk;
-    first_block(P, lane, blk);
+    first_block<TAB>(P, lane, blk);
     // launch telemetry (3 atomics per wave): first start, work queue dry, last exit
     if (lane == 0) atomicMin(&P.counters->t_first, __builtin_amdgcn_s_memrealtime());
     STAMP_DECL;
     for (;;) {
         STAMP(0);
-        refill<MODE, COUNT>(P, lane, st, ps, blk, stamps);
+        refill<MODE, COUNT, TAB>(P, lane, st, ps, blk, stamps);
         if (!saw_dry && __ballot(st == ST_RETIRED)) {   // this wave saw the queue run dry
             saw_dry = true;
             if (lane == 0) atomicMin(&P.counters->t_dry, __builtin_amdgcn_s_memrealtime());
@@ -1921,14 +1953,14 @@ __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4
 }
 
 // LBVH kernel, tree in global memory (A/B reference: every node and leaf from L2).
-template <bool COUNT, int MODE>
+template <bool COUNT, int MODE, bool TAB = false>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_global_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
     stage_walk_params(P, threadIdx.x);
     stage_rows(P, threadIdx.x, kTraceBlock);
     __syncthreads();
-    lbvh_loop<COUNT, LAYOUT_GLOBAL, MODE>(P, reinterpret_cast<const float4*>(P.nodes),
+    lbvh_loop<COUNT, LAYOUT_GLOBAL, MODE, false, false, TAB>(P, reinterpret_cast<const float4*>(P.nodes),
                                           reinterpret_cast<const float4*>(P.leaf_geom), P.leaf_ids,
                                           reinterpret_cast<const float4*>(P.geom),
                                           reinterpret_cast<const float4*>(P.mat));
@@ -1940,7 +1972,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // [nodes | leaf spheres | leaf ids]. The geometry + material records read by
 // shading stay in HBM: one random record per hit is an L2 hit (staging them in LDS measured the
 // same), and the LDS they would take fits bigger trees as octant copies.
-template <bool COUNT, uint32_t NOCT, int MODE>
+template <bool COUNT, uint32_t NOCT, int MODE, bool TAB = false>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_lds_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -1987,7 +2019,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
     stage_walk_params(P, threadIdx.x);
     stage_rows(P, threadIdx.x, kTraceBlock);
     __syncthreads();
-    lbvh_loop<COUNT, NOCT == 8 ? LAYOUT_OCT : LAYOUT_LDS1, MODE>(
+    lbvh_loop<COUNT, NOCT == 8 ? LAYOUT_OCT : LAYOUT_LDS1, MODE, false, false, TAB>(
         P, lds, lds + n_node4, reinterpret_cast<const uint32_t*>(lds + n_node4 + n_leaf4), geom4, mat4);
 }
 
@@ -1996,7 +2028,8 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // REC the shading records in the static table s_rec.
 // FLAT: the grid is one cell thick in y, as every grid of a scene whose small spheres lie in one
 // layer is (configs 3 and 5): the DDA steps x and z only (grid_walk; launch_trace picks it).
-template <bool COUNT, int MODE, bool IN_LDS, bool COOP = false, bool REC = false, bool CQ = false, bool FLAT = false>
+template <bool COUNT, int MODE, bool IN_LDS, bool COOP = false, bool REC = false, bool CQ = false, bool FLAT = false,
+          bool TAB = false>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_grid_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -2005,7 +2038,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
         stage_walk_params(P, threadIdx.x);
         stage_rows(P, threadIdx.x, kTraceBlock);
         __syncthreads();
-        lbvh_loop<COUNT, COOP ? LAYOUT_GRID_COOP : LAYOUT_GRID_L2, MODE, false, FLAT>(P, reinterpret_cast<const float4*>(P.cell_start),
+        lbvh_loop<COUNT, COOP ? LAYOUT_GRID_COOP : LAYOUT_GRID_L2, MODE, false, FLAT, TAB>(P, reinterpret_cast<const float4*>(P.cell_start),
                                             reinterpret_cast<const float4*>(P.grid_rec), P.grid_ids,
                                             reinterpret_cast<const float4*>(P.geom),
                                             reinterpret_cast<const float4*>(P.mat));
@@ -2031,12 +2064,12 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
             s_rec[3 * i + 2] = mat4[2 * i + 1];
         }
         __syncthreads();
-        lbvh_loop<COUNT, CQ ? LAYOUT_GRID_CQ : LAYOUT_GRID, MODE, true, FLAT>(P, reinterpret_cast<const float4*>(cst), lds,
+        lbvh_loop<COUNT, CQ ? LAYOUT_GRID_CQ : LAYOUT_GRID, MODE, true, FLAT, TAB>(P, reinterpret_cast<const float4*>(cst), lds,
                                                                               ids, s_rec, s_rec);   // (load_hit_rec)
         return;
     }
     __syncthreads();
-    lbvh_loop<COUNT, COOP ? LAYOUT_GRID_COOP : CQ ? LAYOUT_GRID_CQ : LAYOUT_GRID, MODE, false, FLAT>(P, reinterpret_cast<const float4*>(cst), lds, ids,
+    lbvh_loop<COUNT, COOP ? LAYOUT_GRID_COOP : CQ ? LAYOUT_GRID_CQ : LAYOUT_GRID, MODE, false, FLAT, TAB>(P, reinterpret_cast<const float4*>(cst), lds, ids,
                                         reinterpret_cast<const float4*>(P.geom),
                                         reinterpret_cast<const float4*>(P.mat));
 }
@@ -2044,7 +2077,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // LBVH kernel for trees too big for LDS: the treelet (rt_build.hip build_treelet) is staged in LDS
 // with its rank links turned into LDS addresses; leaves, subtrees below the cut, geometry and
 // materials stay in HBM/L2.
-template <bool COUNT, int MODE>
+template <bool COUNT, int MODE, bool TAB = false>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_top_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -2063,7 +2096,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
     stage_walk_params(P, threadIdx.x);
     stage_rows(P, threadIdx.x, kTraceBlock);
     __syncthreads();
-    lbvh_loop<COUNT, LAYOUT_TOP, MODE>(P, lds, reinterpret_cast<const float4*>(P.leaf_geom), P.leaf_ids,
+    lbvh_loop<COUNT, LAYOUT_TOP, MODE, false, false, TAB>(P, lds, reinterpret_cast<const float4*>(P.leaf_geom), P.leaf_ids,
                                        reinterpret_cast<const float4*>(P.geom),
                                        reinterpret_cast<const float4*>(P.mat));
 }
@@ -2226,54 +2259,52 @@ __global__ __launch_bounds__(256) void rt_debug_exact_kernel(uint64_t base, floa
 // ---- host-callable launchers (rt_api.cpp) ---------------------------------------------------
 namespace rt {
 
-template <int MODE>
+// TAB: the table form of the hand-out (TraceParams::block_tab), HASH launches only.
+template <int MODE, bool TAB>
 static const void* pick_mode(uint32_t accel, bool count, bool flat) {
 #define RT_FN(...) reinterpret_cast<const void*>(__VA_ARGS__)
+#define RT_GRID(C, IN_LDS, COOP, REC, CQ, FLAT) RT_FN(rt_trace_grid_kernel<C, MODE, IN_LDS, COOP, REC, CQ, FLAT, TAB>)
     if (flat && !count) {   // the grid walks of one-layer grids (instrumented builds count the same cells)
         switch (accel) {
-            case ACCEL_GRID: return RT_FN(rt_trace_grid_kernel<false, MODE, true, false, false, false, true>);
-            case ACCEL_GRID_REC: return RT_FN(rt_trace_grid_kernel<false, MODE, true, false, true, false, true>);
-            case ACCEL_GRID_GLOBAL: return RT_FN(rt_trace_grid_kernel<false, MODE, false, false, false, false, true>);
+            case ACCEL_GRID: return RT_GRID(false, true, false, false, false, true);
+            case ACCEL_GRID_REC: return RT_GRID(false, true, false, true, false, true);
+            case ACCEL_GRID_GLOBAL: return RT_GRID(false, false, false, false, false, true);
             default: break;
         }
     }
     switch (accel) {
         case ACCEL_BRUTE:
-            return count ? RT_FN(rt_trace_brute_kernel<true, MODE>) : RT_FN(rt_trace_brute_kernel<false, MODE>);
+            return count ? RT_FN(rt_trace_brute_kernel<true, MODE, TAB>) : RT_FN(rt_trace_brute_kernel<false, MODE, TAB>);
         case ACCEL_LBVH_LDS:
-            return count ? RT_FN(rt_trace_lds_kernel<true, 1u, MODE>) : RT_FN(rt_trace_lds_kernel<false, 1u, MODE>);
+            return count ? RT_FN(rt_trace_lds_kernel<true, 1u, MODE, TAB>) : RT_FN(rt_trace_lds_kernel<false, 1u, MODE, TAB>);
         case ACCEL_LBVH_OCT:
-            return count ? RT_FN(rt_trace_lds_kernel<true, 8u, MODE>) : RT_FN(rt_trace_lds_kernel<false, 8u, MODE>);
+            return count ? RT_FN(rt_trace_lds_kernel<true, 8u, MODE, TAB>) : RT_FN(rt_trace_lds_kernel<false, 8u, MODE, TAB>);
         case ACCEL_LBVH_TOP:
-            return count ? RT_FN(rt_trace_top_kernel<true, MODE>) : RT_FN(rt_trace_top_kernel<false, MODE>);
+            return count ? RT_FN(rt_trace_top_kernel<true, MODE, TAB>) : RT_FN(rt_trace_top_kernel<false, MODE, TAB>);
         case ACCEL_GRID:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, true>) : RT_FN(rt_trace_grid_kernel<false, MODE, true>);
+            return count ? RT_GRID(true, true, false, false, false, false) : RT_GRID(false, true, false, false, false, false);
         case ACCEL_GRID_COOP:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, true, true>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, true, true>);
+            return count ? RT_GRID(true, true, true, false, false, false) : RT_GRID(false, true, true, false, false, false);
         case ACCEL_GRID_REC:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, true, false, true>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, true, false, true>);
+            return count ? RT_GRID(true, true, false, true, false, false) : RT_GRID(false, true, false, true, false, false);
         case ACCEL_GRID_CQ:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, true, false, false, true>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, true, false, false, true>);
+            return count ? RT_GRID(true, true, false, false, true, false) : RT_GRID(false, true, false, false, true, false);
         case ACCEL_GRID_REC_CQ:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, true, false, true, true>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, true, false, true, true>);
+            return count ? RT_GRID(true, true, false, true, true, false) : RT_GRID(false, true, false, true, true, false);
         case ACCEL_GRID_GLOBAL_COOP:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, false, true>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, false, true>);
+            return count ? RT_GRID(true, false, true, false, false, false) : RT_GRID(false, false, true, false, false, false);
         case ACCEL_GRID_GLOBAL:
-            return count ? RT_FN(rt_trace_grid_kernel<true, MODE, false>)
-                         : RT_FN(rt_trace_grid_kernel<false, MODE, false>);
+            return count ? RT_GRID(true, false, false, false, false, false) : RT_GRID(false, false, false, false, false, false);
         default:
-            return count ? RT_FN(rt_trace_global_kernel<true, MODE>) : RT_FN(rt_trace_global_kernel<false, MODE>);
+            return count ? RT_FN(rt_trace_global_kernel<true, MODE, TAB>) : RT_FN(rt_trace_global_kernel<false, MODE, TAB>);
     }
+#undef RT_GRID
 #undef RT_FN
 }
 
-static const void* pick(uint32_t accel, bool count, int mode, bool flat) {
-    return mode == MODE_HASH ? pick_mode<MODE_HASH>(accel, count, flat) : pick_mode<MODE_STREAM>(accel, count, flat);
+static const void* pick(uint32_t accel, bool count, int mode, bool flat, bool tab = false) {
+    if (mode != MODE_HASH) return pick_mode<MODE_STREAM, false>(accel, count, flat);
+    return tab ? pick_mode<MODE_HASH, true>(accel, count, flat) : pick_mode<MODE_HASH, false>(accel, count, flat);
 }
 
 bool flat_grid_form(const TraceParams& P, uint32_t accel, bool count) {
@@ -2287,7 +2318,9 @@ uint32_t block_size(uint32_t accel) { return accel == ACCEL_BRUTE ? kBruteBlock 
 hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
                         hipStream_t st) {
     void* args[] = {const_cast<TraceParams*>(&P)};
-    return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count)), dim3(grid), dim3(block_size(accel)),
+    // (the table form's occupancy is its uniform twin's: the same launch bounds and LDS)
+    return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count), P.block_tab != nullptr), dim3(grid),
+                           dim3(block_size(accel)),
                            args, lds_bytes, st);
 }
 

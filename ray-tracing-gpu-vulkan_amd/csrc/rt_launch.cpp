@@ -303,6 +303,13 @@ int split_units(const Inputs& in, Plan& P, uint32_t spp, uint64_t pixels, uint64
     P.head_tiles = uint32_t(head_tiles);
     P.head_chunks = uint32_t(head_tiles ? head_chunks : chunks);
     P.n_units = uint32_t((head_tiles * P.head_chunks + (n_tiles - head_tiles) * chunks) * 64u);
+    hand_out_units(in, P, tile_order);
+    return 0;
+}
+
+void hand_out_units(const Inputs& in, Plan& P, bool tile_order) {
+    const int mode = int(P.mode);
+    const uint64_t blk = P.block;
     const uint64_t full = uint64_t(in.cu_count) * P.blocks_per_cu;
     const uint64_t by_work = (uint64_t(P.n_units) + blk - 1) / blk;
     const int grid = int(std::max<uint64_t>(1, std::min(full, by_work)));
@@ -321,7 +328,6 @@ int split_units(const Inputs& in, Plan& P, uint32_t spp, uint64_t pixels, uint64
         const uint64_t iso = uint64_t(Tuning::get(in.tune.isolate_tiles, double(uint64_t(grid) * blk / 64u / 512u)));
         P.isolate_blocks = (tile_order && mode == rt::MODE_STREAM) ? uint32_t(std::min<uint64_t>(P.first_blocks, iso)) : 0u;
     }
-    return 0;
 }
 
 int make_plan(const Inputs& in, const Device& dev, Plan& p, const char** err) {

@@ -149,6 +149,11 @@ int plan_form(const Inputs& in, const Device& dev, Plan& p, const char** err);
 int split_units(const Inputs& in, Plan& p, uint32_t spp, uint64_t pixels, uint64_t n_tiles, bool tile_order,
                 bool head_tail, const char** err);
 
+// The tail of split_units, for any launch whose p.n_units is set (a uniform split's, or 64 x the
+// entries of a block table, rt_sample_map.h): the grid size and the block hand-out (n_block_units,
+// first_blocks, isolate_blocks; the refill_reserve rule).
+void hand_out_units(const Inputs& in, Plan& p, bool tile_order);
+
 // Both halves for the band of `in` (rt_debug_launch_plan without a context).
 int make_plan(const Inputs& in, const Device& dev, Plan& p, const char** err);
 

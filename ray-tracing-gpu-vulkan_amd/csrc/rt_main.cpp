@@ -21,6 +21,9 @@
 //   frame (rt_render_sample_map_device) that replays the latest adaptive frame's per-tile counts
 //   without the pass loop, queued asynchronously; duration_per_frame adds the replays and the mean
 //   spp. --replay without --adaptive and --frames is refused.
+//   --map-launch levels|one: the schedule of the replays (rt_sample_map_set_schedule): one trace
+//   launch per distinct count (default), or one launch of a block table for the whole frame.
+//   Refused without --replay; duration_per_frame names it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -175,7 +178,7 @@ int run_adaptive(uint32_t samples, uint32_t width, uint32_t height, bool store, 
 // i % (replay + 1) == 0, else a sample-map frame replaying the latest adaptive frame's counts. One
 // stream, the scene rebuilt per frame as run_frames does; the replays are queued without a host wait.
 int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate, bool store,
-                        const rt_adaptive& ad, uint32_t replay) {
+                        const rt_adaptive& ad, uint32_t replay, uint32_t map_schedule) {
     rt_context* ctx = nullptr;
     rt_sample_map* map = nullptr;
     hipStream_t stream = nullptr;
@@ -184,6 +187,7 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     CLI_HIP(hipSetDevice(0));
     CLI_RT(rt_context_create(0, &ctx));
     CLI_RT(rt_sample_map_create(ctx, width, height, &map));
+    CLI_RT(rt_sample_map_set_schedule(map, map_schedule, 0));
     CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     CLI_HIP(hipMalloc(&accum, size_t(width) * height * 16));
     CLI_HIP(hipMalloc(&rgba8, size_t(width) * height * 4));
@@ -239,9 +243,10 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         CLI_HIP(hipStreamSynchronize(stream));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
         done += k;
-        std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u replays, mean %.2f spp of at most "
-                    "%u, %.1f Msamples/s)\n",
-                    sec / k * 1e3, k, double(ad.threshold), window_replays, double(window_samples) / pixels / k, samples,
+        std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u replays, map launch %s, mean %.2f spp "
+                    "of at most %u, %.1f Msamples/s)\n",
+                    sec / k * 1e3, k, double(ad.threshold), window_replays,
+                    map_schedule == RT_SAMPLE_MAP_ONE_LAUNCH ? "one" : "levels", double(window_samples) / pixels / k, samples,
                     double(window_samples) / sec / 1e6);
     }
     if (store) {   // the last frame
@@ -280,8 +285,8 @@ bool parse_adaptive(const char* s, rt_adaptive& ad) {
 
 int main(int argc, const char** argv) {
     uint32_t samples = 10, width = 1920, height = 1080, gpu_count = 1, frames = 0, rng_mode = RT_RNG_PIXEL_STREAM;
-    uint32_t replay = 0;
-    bool rng_explicit = false, replay_given = false;
+    uint32_t replay = 0, map_schedule = RT_SAMPLE_MAP_LEVELS;
+    bool rng_explicit = false, replay_given = false, map_launch_given = false;
     bool store = false, animate = false, adaptive = false;
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
@@ -301,6 +306,8 @@ int main(int argc, const char** argv) {
             std::puts("                                  # tiles noisier than thr, at most --samples per pixel");
             std::puts("--replay <count>                  # With --adaptive and --frames: after each adaptive frame, count");
             std::puts("                                  # frames replay its per-tile sample counts (no pass loop)");
+            std::puts("--map-launch <levels|one>         # With --replay: a launch per distinct count (default) or one");
+            std::puts("                                  # launch of a block table per replayed frame");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -320,6 +327,13 @@ int main(int argc, const char** argv) {
             }
             rng_mode = std::strcmp(argv[++i], "hash") == 0 ? RT_RNG_SAMPLE_HASH : RT_RNG_PIXEL_STREAM;
             rng_explicit = true;
+        } else if (a == "--map-launch") {
+            if (i + 1 >= argc || (std::strcmp(argv[i + 1], "levels") != 0 && std::strcmp(argv[i + 1], "one") != 0)) {
+                std::fprintf(stderr, "--map-launch needs levels or one\n");
+                return 2;
+            }
+            map_schedule = std::strcmp(argv[++i], "one") == 0 ? RT_SAMPLE_MAP_ONE_LAUNCH : RT_SAMPLE_MAP_LEVELS;
+            map_launch_given = true;
         } else if (a == "--samples" || a == "--width" || a == "--height" || a == "--gpus" || a == "--frames" ||
                    a == "--replay") {
             uint32_t v = 0;
@@ -342,6 +356,10 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "--replay needs --adaptive and --frames\n");
         return 2;
     }
+    if (map_launch_given && !replay_given) {
+        std::fprintf(stderr, "--map-launch needs --replay (with --adaptive and --frames)\n");
+        return 2;
+    }
     if (adaptive) {   // refused before anything renders
         if (rng_explicit && rng_mode != RT_RNG_SAMPLE_HASH) {
             std::fprintf(stderr, "--adaptive needs the counter-based stream: it cannot run with --rng stream\n");
@@ -357,7 +375,7 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
-    if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay);
+    if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay, map_schedule);
     if (adaptive) return run_adaptive(samples, width, height, store, ad);
     if (frames > 0) return run_frames(samples, width, height, gpu_count, frames, animate, store, rng_mode);
     // ray_trace() keeps the reference's signature; its stream is selected through RT_RNG. An

@@ -12,9 +12,9 @@ int refuse(std::string* err, const std::string& msg) {
     if (err) *err = msg;
     return RT_ERR_INVALID_ARGUMENT;
 }
-}  // namespace
 
-int make_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, Plan& p, std::string* err) {
+int plan_levels(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint64_t max_levels, Plan& p,
+                std::string* err) {
     if (n_tiles != 0 && !tile_counts) return refuse(err, "tile_counts is NULL");
     const uint64_t q = quantum > 1u ? quantum : 1u;
     Plan r;
@@ -40,19 +40,28 @@ int make_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, P
         if (n == 0u) break;
         if (i + 1u == n_tiles || r.quantised[r.order[i + 1u]] != n) {
             n_levels++;
-            if (n_levels <= kMaxLevels) {
+            if (n_levels <= max_levels) {
                 r.levels.push_back(n);
                 r.level_tiles.push_back(i + 1u);
             }
         }
     }
-    if (n_levels > kMaxLevels)
+    if (n_levels > max_levels)
         return refuse(err, "the table has " + std::to_string(n_levels) + " levels (distinct non-zero counts), more than " +
                                std::to_string(kMaxLevels) + ": pass a quantum that rounds the counts to fewer");
     std::reverse(r.levels.begin(), r.levels.end());
     std::reverse(r.level_tiles.begin(), r.level_tiles.end());
     p = std::move(r);
     return RT_OK;
+}
+}  // namespace
+
+int make_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, Plan& p, std::string* err) {
+    return plan_levels(tile_counts, n_tiles, quantum, kMaxLevels, p, err);
+}
+
+int make_plan_any_levels(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, Plan& p, std::string* err) {
+    return plan_levels(tile_counts, n_tiles, quantum, ~0ull, p, err);
 }
 
 int totals(const Plan& p, uint32_t band_w, uint32_t band_h, rt_sample_map_info* out, std::string* err) {
@@ -86,6 +95,85 @@ int plan_arrays(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum,
     if (levels) std::copy(p.levels.begin(), p.levels.end(), levels);
     if (level_tiles) std::copy(p.level_tiles.begin(), p.level_tiles.end(), level_tiles);
     if (n_levels) *n_levels = uint32_t(p.levels.size());
+    return RT_OK;
+}
+
+uint64_t count_blocks(const Plan& p, uint32_t unit) {
+    uint64_t n = 0;
+    for (uint32_t t : p.order) {
+        const uint32_t c = p.quantised[t];
+        if (c == 0u) break;   // the order ends with the zero tiles
+        n += (uint64_t(c) + unit - 1u) / unit;
+    }
+    return n;
+}
+
+uint32_t auto_unit(const Plan& p) {
+    uint64_t total = 0;
+    for (uint32_t c : p.quantised) total += 64u * uint64_t(c);
+    const uint64_t max_count = p.levels.empty() ? 0u : p.levels.back();
+    const uint64_t floor = std::min<uint64_t>(128u, std::max<uint64_t>(32u, max_count / 32u));
+    const uint64_t per_unit = kNominalLanes * 128u;
+    uint64_t unit = std::max(floor, (total + per_unit - 1u) / per_unit);
+    unit = std::min<uint64_t>(unit, kMaxUnit);
+    while (unit < kMaxUnit && count_blocks(p, uint32_t(unit)) > kMaxBlocks) unit = std::min<uint64_t>(unit * 2u, kMaxUnit);
+    return uint32_t(unit);
+}
+
+int make_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t unit_samples,
+                    BlockPlan& bp, std::string* err) {
+    if (unit_samples > kMaxUnit)
+        return refuse(err, "unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
+    BlockPlan r;
+    if (int rc = make_plan_any_levels(tile_counts, n_tiles, quantum, r.plan, err)) return rc;
+    const uint32_t unit = unit_samples ? unit_samples : auto_unit(r.plan);
+    const uint64_t n_blocks = count_blocks(r.plan, unit);
+    if (n_blocks > kMaxBlocks) {
+        // count_blocks falls as the unit grows: the smallest unit that fits, by bisection
+        if (count_blocks(r.plan, kMaxUnit) > kMaxBlocks)
+            return refuse(err, "the table has " + std::to_string(count_blocks(r.plan, kMaxUnit)) +
+                                   " non-zero tiles: no block table of it has unit ids of 32 bits");
+        uint32_t lo = unit, hi = kMaxUnit;   // lo does not fit, hi does
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            (count_blocks(r.plan, mid) > kMaxBlocks ? lo : hi) = mid;
+        }
+        return refuse(err, "unit_samples = " + std::to_string(unit) + " gives " + std::to_string(n_blocks) +
+                               " blocks, more than 2^25 - 1 (unit ids of 32 bits): the smallest unit_samples that fits is " +
+                               std::to_string(hi));
+    }
+    r.unit_samples = unit;
+    r.blocks.reserve(size_t(n_blocks));
+    for (uint32_t t : r.plan.order) {
+        const uint64_t n = r.plan.quantised[t];
+        if (n == 0u) break;
+        r.live_tiles++;
+        const uint64_t k = (n + unit - 1u) / unit;
+        for (uint64_t c = 0; c < k; c++) r.blocks.push_back(Block{t, uint32_t(c * n / k), uint32_t((c + 1u) * n / k), 0u});
+    }
+    bp = std::move(r);
+    return RT_OK;
+}
+
+int block_plan_arrays(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t unit_samples,
+                      uint32_t* blocks_out, uint64_t capacity, uint64_t* n_blocks, uint32_t* unit_samples_used,
+                      std::string* err) {
+    BlockPlan bp;
+    if (int rc = make_block_plan(tile_counts, n_tiles, quantum, unit_samples, bp, err)) return rc;
+    if (blocks_out && capacity < bp.blocks.size())
+        return refuse(err, "capacity " + std::to_string(capacity) + " is below the table's " +
+                               std::to_string(bp.blocks.size()) + " blocks");
+    if (blocks_out) {
+        for (size_t b = 0; b < bp.blocks.size(); b++) {
+            const Block& e = bp.blocks[b];
+            blocks_out[4u * b] = e.tile;
+            blocks_out[4u * b + 1u] = e.s0;
+            blocks_out[4u * b + 2u] = e.s1;
+            blocks_out[4u * b + 3u] = 0u;
+        }
+    }
+    if (n_blocks) *n_blocks = bp.blocks.size();
+    if (unit_samples_used) *unit_samples_used = bp.unit_samples;
     return RT_OK;
 }
 

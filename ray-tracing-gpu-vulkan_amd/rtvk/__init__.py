@@ -29,7 +29,7 @@ __all__ = [
     "make_options", "Renderer", "MultiRenderer", "render", "ray_trace", "store_ppm", "spheres_to_numpy",
     "load_library", "HASH", "STREAM", "multi_plan", "launch_inputs", "launch_plan", "row_weights", "struct_dict", "partition_strips", "partition_rebalance",
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
-    "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info",
+    "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -475,6 +475,28 @@ class SampleMap:
         check(self._lib.rt_sample_map_get_info(self._map, ctypes.byref(info)))
         return info
 
+    def schedule(self, schedule: int, unit_samples: int = 0) -> None:
+        """The schedule the next set call plans by (rt_sample_map_set_schedule): abi.SAMPLE_MAP_LEVELS
+        (the default: one launch per distinct count) or abi.SAMPLE_MAP_ONE_LAUNCH (one launch of a block
+        table, any number of distinct counts) with units of at most unit_samples samples (0: automatic)."""
+        check(self._lib.rt_sample_map_set_schedule(self._map, schedule, unit_samples))
+
+    def schedule_info(self) -> dict:
+        """{schedule, unit_samples, n_blocks} of the plan the map holds (rt_sample_map_get_schedule)."""
+        sched, unit, nb = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        check(self._lib.rt_sample_map_get_schedule(self._map, ctypes.byref(sched), ctypes.byref(unit), ctypes.byref(nb)))
+        return {"schedule": sched.value, "unit_samples": unit.value, "n_blocks": nb.value}
+
+    def debug_blocks(self):
+        """The block table the device holds (rt_debug_sample_map_blocks): uint32 [n_blocks, 4] rows
+        (tile, s0, s1, 0), empty for a level plan."""
+        nb = ctypes.c_uint64(0)
+        check(self._lib.rt_debug_sample_map_blocks(self._map, None, 0, ctypes.byref(nb)))
+        blocks = np.zeros((nb.value, 4), np.uint32)
+        if nb.value:
+            check(self._lib.rt_debug_sample_map_blocks(self._map, blocks.ctypes.data, nb.value, ctypes.byref(nb)))
+        return blocks
+
     def debug_plan(self) -> dict:
         """What the device holds after the last set call (rt_debug_sample_map), in sample_map_plan's form."""
         n = self.tiles_x * self.tiles_y
@@ -483,9 +505,26 @@ class SampleMap:
         level_tiles = np.zeros(abi.SAMPLE_MAP_MAX_LEVELS, np.uint32)
         check(self._lib.rt_debug_sample_map(self._map, order.ctypes.data, levels.ctypes.data, level_tiles.ctypes.data,
                                             quantised.ctypes.data))
-        j = self.info.levels
+        j = min(self.info.levels, abi.SAMPLE_MAP_MAX_LEVELS)
         return {"order": order, "levels": levels[:j].copy(), "level_tiles": level_tiles[:j].copy(),
                 "quantised": quantised}
+
+
+def sample_map_block_plan(counts, quantum: int = 0, unit_samples: int = 0) -> dict:
+    """The block table of a host table under SAMPLE_MAP_ONE_LAUNCH (rt_sample_map_block_plan; host
+    only): {blocks: uint32 [n_blocks, 4] rows (tile, s0, s1, 0), unit_samples: the U used}. unit_samples
+    0: automatic. Raises RtError for what the library refuses (a count or unit above 2^19, a table of
+    2^25 blocks or more)."""
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.uint32)
+    n = len(c)
+    lib = load_library()
+    nb, used = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    check(lib.rt_sample_map_block_plan(c.ctypes.data if n else None, n, quantum, unit_samples, None, 0,
+                                       ctypes.byref(nb), ctypes.byref(used)))
+    blocks = np.zeros((nb.value, 4), np.uint32)
+    check(lib.rt_sample_map_block_plan(c.ctypes.data if n else None, n, quantum, unit_samples,
+                                       blocks.ctypes.data if nb.value else None, nb.value, None, None))
+    return {"blocks": blocks, "unit_samples": used.value}
 
 
 def sample_map_plan(counts, quantum: int = 0) -> dict:

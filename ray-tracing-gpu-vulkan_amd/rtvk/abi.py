@@ -102,6 +102,8 @@ class AdaptiveInfo(ctypes.Structure):
 
 SAMPLE_MAP_MAX_LEVELS = 64   # RT_SAMPLE_MAP_MAX_LEVELS
 SAMPLE_MAP_MAX_COUNT = 1 << 19
+SAMPLE_MAP_LEVELS = 0        # RT_SAMPLE_MAP_LEVELS: one launch per distinct count (the default)
+SAMPLE_MAP_ONE_LAUNCH = 1    # RT_SAMPLE_MAP_ONE_LAUNCH: the whole frame is one launch of a block table
 
 
 class SampleMapInfo(ctypes.Structure):
@@ -156,7 +158,7 @@ assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and A
 assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
-_P, _U32, _I = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int
+_P, _U32, _I, _U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
 EXPORTS = {
     "rt_abi_version": (_U32, []),
     "rt_last_error": (ctypes.c_char_p, []),
@@ -184,6 +186,10 @@ EXPORTS = {
                                          ctypes.POINTER(Options), _P, _P]),
     "rt_sample_map_plan": (_I, [_P, _U32, _U32, _P, _P, _P, ctypes.POINTER(_U32), _P]),
     "rt_debug_sample_map": (_I, [_P, _P, _P, _P, _P]),
+    "rt_sample_map_set_schedule": (_I, [_P, _U32, _U32]),
+    "rt_sample_map_get_schedule": (_I, [_P, ctypes.POINTER(_U32), ctypes.POINTER(_U32), ctypes.POINTER(_U64)]),
+    "rt_sample_map_block_plan": (_I, [_P, _U32, _U32, _U32, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
+    "rt_debug_sample_map_blocks": (_I, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     "rt_debug_sample_map_info": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(SampleMapInfo)]),
     "rt_get_stats": (_I, [_P, ctypes.POINTER(Stats)]),
     "rt_launch_ms": (_I, [_P, _U32, ctypes.POINTER(ctypes.c_float)]),

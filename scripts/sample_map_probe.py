@@ -6,6 +6,9 @@ cap 10 000 spp, min = step = 512), per threshold:
   replay       rt_render_sample_map_device replaying that frame's counts (set_from_adaptive, quantum 0),
                with the per-level trace-kernel times (rt_launch_ms);
   replay_q     the same at --quantum (fewer levels, more samples);
+  replay_one   the replay under the one-launch schedule (RT_SAMPLE_MAP_ONE_LAUNCH), once per unit
+               length of --units (0: automatic), with the launch's kernel time and its t_dry / t_last
+               tail; asserted to be the level replay's image bit for bit;
   uniform      rt_render_device at the adaptive frame's mean spp, rounded up to even: the frame of the
                same cost;
   and the PSNR of each rgba8 frame against the uniform frame at the cap (skipped with --no-psnr).
@@ -13,9 +16,11 @@ cap 10 000 spp, min = step = 512), per threshold:
 --lib PATH loads another build of the library (e.g. the parent commit's, for the adaptive leg's A/B);
 a build without the sample-map entry points measures the adaptive leg only. Prints one JSON line per
 measurement; every time is the list of --repeat frames, host clock around a synchronised frame.
-  python scripts/sample_map_probe.py [--thresholds 0.04,0.02] [--quantum 2048] [--lib PATH] [--no-psnr]
+  python scripts/sample_map_probe.py [--thresholds 0.04,0.02] [--quantum 2048] [--units 0,32,64,128,256]
+                                     [--lib PATH] [--no-psnr]
 """
 import argparse
+import ctypes
 import json
 import sys
 import time
@@ -41,6 +46,7 @@ def main() -> int:
     ap.add_argument("--step", type=int, default=512)
     ap.add_argument("--thresholds", default="0.04,0.02")
     ap.add_argument("--quantum", type=int, default=2048)
+    ap.add_argument("--units", default="0,32,64,128,256", help="unit lengths of the one-launch replay (0: automatic)")
     ap.add_argument("--repeat", type=int, default=2, help="timed frames per measurement")
     ap.add_argument("--lib", default=None, help="another build of librt_mi355x.so")
     ap.add_argument("--no-psnr", action="store_true", help="skip the uniform frame at the cap and the PSNRs")
@@ -53,6 +59,7 @@ def main() -> int:
     if args.lib:
         abi._lib = abi.load_library(args.lib)
     has_maps = hasattr(abi.load_library(), "rt_render_sample_map_device")
+    has_one = hasattr(abi.load_library(), "rt_sample_map_set_schedule")
     W, H, cap = args.width, args.height, args.spp
     lib_sha = abi.build_info().get("sources_sha256")
     acc = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
@@ -104,6 +111,25 @@ def main() -> int:
                                   "level_trace_kernel_ms": levels, "sum_level_ms": round(sum(levels), 2),
                                   "frame_minus_trace_kernels_ms": round(ms[-1] - sum(levels), 2),
                                   "psnr_db": None if ref is None else psnr(out.cpu().numpy(), ref)}), flush=True)
+                if name == "replay":
+                    level_acc, level_out = acc.clone(), out.clone()
+            for unit in [int(u) for u in args.units.split(",") if u] if has_one else []:
+                smap.schedule(abi.SAMPLE_MAP_ONE_LAUNCH, unit)
+                mi = smap.set_from_adaptive(0)
+                sched = smap.schedule_info()
+                r.render_sample_map(rci, acc, out, smap, options=opt)   # warm-up
+                _, ms = timed(lambda: r.render_sample_map(rci, acc, out, smap, options=opt))
+                assert torch.equal(acc, level_acc) and torch.equal(out, level_out), "one-launch replay differs from the level replay"
+                h = (ctypes.c_uint64 * 68)()   # the last launch's realtime stamps, 100 MHz (scripts/tail_ab.py)
+                abi.check(abi.load_library().rt_debug_lane_hist(r._ctx, h))
+                kt = {"queue_dry_ms": round((h[66] - h[65]) / 1e5, 2), "tail_ms": round((h[67] - h[66]) / 1e5, 2)}
+                print(json.dumps({"what": "replay_one", **base, "unit_samples": unit, "unit_samples_used": sched["unit_samples"],
+                                  "n_blocks": sched["n_blocks"], "frame_ms": ms, "levels": mi.levels,
+                                  "mean_spp": round(mi.samples / (W * H), 1), "tiles": mi.tile_launches,
+                                  "trace_kernel_ms": round(r.launch_ms(0), 3), **kt,
+                                  "same_image_as_replay": True}), flush=True)
+            if has_one:
+                smap.schedule(abi.SAMPLE_MAP_LEVELS)
             even = int(np.ceil(mean_spp / 2.0)) * 2
             rci_u = rtvk.canonical_render_call_info(even, W, H)
             r.render_device(rci_u, acc, out, options=opt)   # warm-up: the tile order of this launch
