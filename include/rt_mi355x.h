@@ -333,6 +333,80 @@ int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t q
 int rt_sample_map_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum,
                              uint32_t unit_samples, uint32_t* blocks_out, uint64_t capacity,
                              uint64_t* n_blocks, uint32_t* unit_samples_used);
+/*
+ * The set call without a host wait: the count table stays on the device. Queued on `stream` behind
+ * every frame already queued on the map (events), a device planner builds what
+ * rt_sample_map_set_device builds on the host under RT_SAMPLE_MAP_ONE_LAUNCH: every count clamped to
+ * count_cap (<= 2^19), the order, the clamped table the resolve divides by and the block table of
+ * rt_sample_map_block_plan(clamped counts, 0, U). No quantum.
+ *   unit_samples   U0: the first unit tried; 0 = clamp(count_cap / 32, 32, 128) (the floor of the
+ *                  automatic unit; its other term needs the table's sum, which the host does not have).
+ *                  U is the smallest U0 2^j (held at 2^19) whose table fits the map's block capacity,
+ *                  min(tiles x ceil(count_cap / U0), 2^22 entries); rt_sample_map_device_unit below
+ *                  computes the same on the host.
+ * The map becomes "device-planned": the host knows count_cap alone, rt_render_sample_map_device checks
+ * samplesPerRenderCall against count_cap and launches the full persistent grid, which reads the
+ * table's size from device memory. rt_sample_map_get_info (tiles, max_count, samples, tile_launches;
+ * levels and min_count are 0) and rt_sample_map_get_schedule copy the planner's summary back: they
+ * wait for the planner, the one synchronisation such a map has, and it is optional. The planner's
+ * buffers are allocated by the first call and the block table grows here only (a growth waits for
+ * the frames that read the old one). A later rt_sample_map_set_device / set_from_adaptive makes the
+ * map host-planned again. RT_ERR_INVALID_ARGUMENT: a NULL argument, count_cap or unit_samples above
+ * 2^19, a band of more than 2^22 tiles; the map keeps what it held. A device error after the first
+ * planner step leaves the map unset.
+ */
+int rt_sample_map_set_device_async(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t unit_samples,
+                                   uint32_t count_cap, void* stream);
+/* The unit the device planner chooses for a host table (host only): the smallest unit0 2^j (unit0 = 0:
+ * as above), held at 2^19, whose block table of min(count, count_cap) has at most `capacity` entries.
+ * RT_ERR_INVALID_ARGUMENT: a NULL table, count_cap or unit0 above 2^19, more non-zero tiles than
+ * `capacity` (no unit fits); *unit_used is not written then. */
+int rt_sample_map_device_unit(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t count_cap, uint32_t unit0,
+                              uint64_t capacity, uint32_t* unit_used);
+/*
+ * The feedback rule of sample maps (host only, exact integers): a tile whose n
+ * samples were rendered as two halves has E, S, m as in rt_adaptive_tile_converged; with
+ *   hot  = !converged(E, S, n, m, thr_q16),  cold = converged(E, S, n, m, thr_q16 >> 1)
+ * its next count is hot ? min(max_spp, 2 n) : cold ? max(min_spp, (n / 2 + 1) & ~1) : n; n = 0 stays 0.
+ * E, S < 2^56, n <= 2^19, 1 <= m <= 64, min_spp and max_spp even with 2 <= min_spp <= max_spp <= 2^19
+ * (RT_ERR_INVALID_ARGUMENT otherwise).
+ */
+int rt_sample_map_feedback_count(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16,
+                                 uint32_t min_spp, uint32_t max_spp, uint32_t* next);
+/*
+ * A feedback frame: the map renders, measures its own noise and plans its
+ * successor on the device; nothing is read back and the call contains no host wait (the buffers'
+ * first allocation and growth aside). Arguments as rt_render_sample_map_device, plus:
+ *   fb             threshold (finite, within [0, 16]), min_spp and max_spp (even, 2 <= min_spp <=
+ *                  max_spp <= 2^19, max_spp <= samplesPerRenderCall), unit_samples (the planner's U0,
+ *                  0: automatic), reserved 0.
+ *   d_tile_error   optional DEVICE array of 2 x tiles uint64: (E, S) of every tile of this frame.
+ * samplesPerRenderCall (the cap) must be even and at least what the map holds. The frame:
+ *   0. on a map not yet planned for feedback at this cap (a host-set one, one set by
+ *      rt_sample_map_set_device_async): its current counts are planned in halves mode first: every
+ *      count rounded up to even, n = 2 h, the block table of the h table over [0, h) (the A half)
+ *      followed by the same entries over [h, n) (the B half);
+ *   1. the A half renders into one set of fixed-point planes, the B half into a second (two launches);
+ *   2. per tile, E and S of rt_adaptive_tile_converged from the two, and its next count by
+ *      rt_sample_map_feedback_count;
+ *   3. the resolve sums both, divides by the map's counts and zeroes both; accum, rgba8 and
+ *      sample_count are those of rt_render_sample_map_device at the rendered (even) counts;
+ *   4. the next counts are planned in halves mode: the map now holds them.
+ * rt_render_sample_map_device on such a map renders both halves in one launch: the same image.
+ * RT_ERR_INVALID_ARGUMENT before any work is queued: rt_render_sample_map_device's refusals, an odd
+ * cap or one below max_spp, the threshold, min_spp / max_spp, unit_samples above 2^19.
+ */
+typedef struct rt_sample_map_feedback {
+    float threshold;
+    uint32_t min_spp, max_spp;
+    uint32_t unit_samples;
+    uint32_t reserved;
+} rt_sample_map_feedback;
+int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                         uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
+                                         uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
+                                         rt_sample_map* map, const rt_sample_map_feedback* fb,
+                                         uint64_t* d_tile_error, void* stream);
 /* Statistics of the last completed rt_render_device (synchronises ctx's last stream). */
 int rt_get_stats(rt_context* ctx, rt_stats* out);
 /* Trace-kernel duration (ms, HIP events on the launch stream) of ctx's launch `back` launches

@@ -108,6 +108,23 @@ int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* lev
  * copied back: 4 words {tile, s0, s1, 0} per block into `out` (`capacity` blocks; NULL: a size
  * query), *n = blocks (0 for a level plan). Waits for the frames queued on the map. */
 int rt_debug_sample_map_blocks(const rt_sample_map* map, uint32_t* out, uint64_t capacity, uint64_t* n);
+/* (For a device-planned map, rt_sample_map_set_device_async, the count is the planner's: the call
+ * waits for the planner.) Tests: the next rt_sample_map_set_device_async calls of `map` plan for a
+ * block capacity of at most max(limit, tiles) entries, so that a small table shows the doubling of
+ * the unit (0: the map's own capacity). */
+int rt_debug_sample_map_limit_blocks(rt_sample_map* map, uint64_t limit);
+/* The block hand-out rule the host plan and the device share (csrc/rt_hand_out.h; host only): of
+ * n_units units, the last `reserve` go out one by one, the others as whole 64-unit blocks, the first
+ * of them to the grid's `grid_waves` waves by wave id. */
+int rt_debug_hand_out(uint32_t n_units, uint64_t reserve, uint64_t grid_waves, uint32_t* n_block_units,
+                      uint32_t* first_blocks);
+/* Host waits so far inside ctx's calls that are documented as queued without one: the growth of the
+ * adaptive planes and of a device-planned map's block table behind queued work. */
+int rt_debug_host_waits(rt_context* ctx, uint64_t* n);
+/* Tests: what the feedback frames of `map` left on the device: the counts the last frame's update
+ * chose (`next`, tiles words; optional) and the tiles all its frames raised and lowered. Waits for
+ * the work queued on the map. */
+int rt_debug_sample_map_feedback(rt_sample_map* map, uint32_t* next, uint64_t* raised, uint64_t* lowered);
 /* The rt_sample_map_info a set call would report for a host table over a band (host only). */
 int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, uint32_t band_height,
                              uint32_t quantum, rt_sample_map_info* out);

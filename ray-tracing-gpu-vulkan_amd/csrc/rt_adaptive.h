@@ -67,4 +67,19 @@ struct AdaptiveErrorParams {
     AdaptiveState* state;
 };
 
+// The update of a feedback frame (rt_render_sample_map_feedback_device): per tile,
+// from the two half-buffers of a frame whose tile t rendered tile_n[t] samples in two halves, the
+// next count by rt::sample_map_feedback_count.
+struct FeedbackParams {
+    const unsigned long long* a;   // half-buffers, as AdaptiveErrorParams
+    const unsigned long long* b;
+    uint64_t texels;
+    uint32_t band_w, band_h, tiles_x, n_tiles;
+    const uint32_t* tile_n;        // per tile: the samples it rendered (even)
+    uint32_t thr_q16, min_spp, max_spp;
+    uint32_t* next;                // out, per tile
+    unsigned long long* tile_error;   // optional out: (E, S) per tile
+    unsigned long long* moved;     // += tiles raised | tiles lowered << 32, one atomic per block
+};
+
 }  // namespace rt

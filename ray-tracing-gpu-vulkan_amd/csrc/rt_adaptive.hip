@@ -9,6 +9,7 @@
 #include "rt_adaptive.h"
 #include "rt_device_math.h"
 #include "rt_internal.h"
+#include "rt_sample_map_feedback.h"
 
 using namespace rtd;
 
@@ -57,6 +58,49 @@ __global__ __launch_bounds__(256) void rt_adaptive_error_kernel(const rt::Adapti
         atomicAdd(&K.state->samples, (unsigned long long)K.n_done * m);
         if (!conv) atomicAdd(&K.state->capped, 1u);
     }
+}
+
+// The update of a feedback frame: rt_adaptive_error_kernel's loads and wave reduction over every tile
+// of the band, lane 0 applies the rule and writes next[t] (and, for callers with a rule of their
+// own, the tile's E and S). No list and no one-address atomic per tile: the counts of raised and
+// lowered tiles go through LDS into one atomic per block.
+__global__ __launch_bounds__(256) void rt_feedback_update_kernel(const rt::FeedbackParams K) {
+    __shared__ unsigned long long s_moved;
+    if (threadIdx.x == 0) s_moved = 0ull;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (t < K.n_tiles) {   // wave-uniform
+        const uint32_t lx = (t % K.tiles_x) * 8u + (lane & 7u);
+        const uint32_t ly = (t / K.tiles_x) * 8u + (lane >> 3);
+        const bool in = lx < K.band_w && ly < K.band_h;
+        unsigned long long e = 0ull, s = 0ull;
+        if (in) {
+            const size_t texel = size_t(ly) * K.band_w + lx;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const unsigned long long a = K.a[c * K.texels + texel], b = K.b[c * K.texels + texel];
+                e += a > b ? a - b : b - a;
+                s += a + b;
+            }
+        }
+        e = wave_sum_u64(e);
+        s = wave_sum_u64(s);
+        const uint32_t m = uint32_t(__popcll(__ballot(in)));
+        if (lane == 0u) {
+            const uint32_t n = K.tile_n[t];
+            const uint32_t next = rt::sample_map_feedback_count(e, s, n, m, K.thr_q16, K.min_spp, K.max_spp);
+            K.next[t] = next;
+            if (K.tile_error) {
+                K.tile_error[2u * t] = e;
+                K.tile_error[2u * t + 1u] = s;
+            }
+            if (next > n) atomicAdd(&s_moved, 1ull);
+            if (next < n) atomicAdd(&s_moved, 1ull << 32);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_moved) atomicAdd(K.moved, s_moved);
 }
 
 // Per texel: total = A + B, stored as rt_resolve_fixed_kernel stores a launch without
@@ -134,6 +178,12 @@ hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st) {
 hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st) {
     if (K.n_list == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_adaptive_error_kernel, dim3((K.n_list + 3u) / 4u), dim3(256), 0, st, K);
+    return hipGetLastError();
+}
+
+hipError_t launch_feedback_update(const FeedbackParams& K, hipStream_t st) {
+    if (K.n_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_feedback_update_kernel, dim3((K.n_tiles + 3u) / 4u), dim3(256), 0, st, K);
     return hipGetLastError();
 }
 

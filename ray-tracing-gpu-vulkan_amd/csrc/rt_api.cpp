@@ -30,6 +30,7 @@
 #include "rt_internal.h"
 #include "rt_launch.h"
 #include "rt_sample_map.h"
+#include "rt_sample_map_feedback.h"
 
 namespace rt {
 hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
@@ -40,6 +41,11 @@ hipError_t launch_resolve_fixed(unsigned long long* fixed, uint64_t n_texels, ui
                                 float* accum, uint8_t* out, hipStream_t st);
 hipError_t launch_tonemap(const float* accum, uint64_t n_texels, uint32_t spp, uint8_t* out, hipStream_t st);
 hipError_t launch_prep(const TraceParams& P, uint32_t work_head, float* tab, uint32_t n_cost, hipStream_t st);
+hipError_t launch_tab_size(const uint32_t* n_blocks, uint64_t reserve, uint64_t grid_waves, TabSize* rec,
+                           Counters* counters, hipStream_t st);
+// rt_sample_map_plan.hip
+hipError_t device_plan_temp_bytes(uint32_t n_tiles, size_t* bytes);
+hipError_t launch_device_plan(const sample_map::DevicePlanParams& K, hipStream_t st);
 uint32_t block_size(uint32_t accel);
 hipError_t launch_scatter_rows(const float* src_acc, const uint8_t* src_px, const uint32_t* rows,
                                uint32_t n_rows, uint32_t width, uint32_t dst_rows, float* dst_acc, uint8_t* dst_px,
@@ -54,6 +60,7 @@ hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);
 hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
                                    uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
                                    uint32_t* sample_count, hipStream_t st);
+hipError_t launch_feedback_update(const FeedbackParams& K, hipStream_t st);
 hipError_t launch_adaptive_store_tiles(const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
                                        const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out,
                                        uint32_t* sample_count, hipStream_t st);
@@ -80,6 +87,7 @@ struct TraceSetup {
     rt::launch::Inputs in;       // what the plan is computed from
     rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
     uint64_t tiles_x = 0, n_tiles = 0;
+    const uint32_t* tab_blocks = nullptr;   // with P.tab_size: the device word that holds the table's block count
 };
 }  // namespace
 
@@ -158,6 +166,9 @@ struct rt_context {
     rt::launch::Inputs last_in;
     // every colour the shaders can return lies in [0, 1] (RT_RNG_SAMPLE_HASH's fixed point needs it)
     bool colours_unit = true;
+    // host waits inside render and set calls that are documented as queued without one (buffer
+    // growth; rt_debug_host_waits: the feedback tests read 0 once the buffers stand)
+    uint64_t host_waits = 0;
     // HIP events bracketing the trace kernel of the last kKernelEvents launches (ring; timing
     // inside a caller's timed region without a host sync per launch, rt_debug_kernel_times)
     static constexpr uint32_t kKernelEvents = 64;
@@ -228,6 +239,25 @@ struct rt_sample_map {
     uint64_t n_blocks = 0, cap_blocks = 0;
     hipEvent_t ev_read = nullptr;
     mutable bool read_pending = false;   // ev_read has been recorded since the last set call
+    // A map planned on the device (rt_sample_map_set_device_async): `table` and `blocks` were written
+    // there, in stream order, and the host knows the cap alone; what the planner found (block count,
+    // unit, totals) stays in `summary` until an info call copies it back. The planner's buffers are
+    // allocated by the first such call.
+    bool device_planned = false;
+    uint32_t count_cap = 0;
+    uint64_t limit_blocks = 0;           // rt_debug_sample_map_limit_blocks (0: none)
+    rt::TabSize* tab_size = nullptr;     // device: the size record of the map's launches, then ...
+    rt::sample_map::DeviceSummary* summary = nullptr;   // ... the planner's summary (one allocation)
+    uint32_t* plan_words = nullptr;      // device: keys, values, sorted keys, offsets (4 x n_tiles)
+    void* plan_temp = nullptr;           // device: the sort's and the scan's scratch
+    size_t plan_temp_bytes = 0;
+    // Feedback frames (rt_render_sample_map_feedback_device): the table is planned in halves mode, one
+    // half of at most half_capacity entries; `next` holds the counts the last frame's update chose
+    // (in plan_words), `moved` the tiles the updates raised | lowered << 32 (behind the summary).
+    bool halves = false;
+    uint64_t half_capacity = 0;
+    uint32_t* next = nullptr;
+    unsigned long long* moved = nullptr;
 };
 
 namespace {
@@ -1276,6 +1306,10 @@ int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
         if (!kev[k]) RT_HIP(hipEventCreate(&kev[k]));
     // counters zeroed, work counter past the first blocks, big-sphere table, tile-cost table zeroed
     RT_HIP(rt::launch_prep(P, P.first_blocks * 64u, ctx->big_tab, P.tile_cost ? uint32_t(n_tiles) : 0u, st));
+    // a table planned on the device: its sizes and the work counter follow from the device's block count
+    if (P.tab_size)
+        RT_HIP(rt::launch_tab_size(S.tab_blocks, rt::launch::refill_reserve(S.in), uint64_t(plan.grid) * plan.block / 64u,
+                                   const_cast<rt::TabSize*>(P.tab_size), P.counters, st));
     P.big_tab = ctx->big_tab;
     RT_HIP(hipEventRecord(kev[0], st));
     RT_HIP(rt::launch_trace(P, accel, plan.count != 0, int(plan.mode), int(plan.grid), plan.lds, st));
@@ -1338,6 +1372,7 @@ int grow_on_stream(T*& buf, uint64_t& cap, uint64_t count, size_t unit, bool zer
 int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStream_t st) {
     rt_context::Adaptive& a = ctx->adaptive;
     if (a.cap < texels) {
+        if (a.planes) ctx->host_waits++;
         if (int rc = grow_on_stream(a.planes, a.cap, texels, 6u * sizeof(unsigned long long), true, st)) return rc;
     }
     if (a.cap_tiles < n_tiles) {
@@ -1423,7 +1458,17 @@ int sample_map_set(rt_sample_map* map, const uint32_t* d_counts, uint32_t quantu
     map->unit_samples = one ? bp.unit_samples : 0u;
     map->n_blocks = one ? bp.blocks.size() : 0u;
     map->set = true;
+    map->device_planned = false;
+    map->halves = false;
     if (info) *info = fresh;
+    return RT_OK;
+}
+
+// The planner's summary of a device-planned map, after a host wait for the planner (and whatever was
+// queued on the map since): the one synchronisation such a map has, in the info calls only.
+int device_summary(const rt_sample_map* map, rt::sample_map::DeviceSummary* s) {
+    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+    RT_HIP(hipMemcpy(s, map->summary, sizeof(*s), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1802,6 +1847,9 @@ int rt_sample_map_destroy(rt_sample_map* map) {
     if (map->read_pending) (void)hipEventSynchronize(map->ev_read);   // the frames that read it
     (void)hipFree(map->table);
     (void)hipFree(map->blocks);
+    (void)hipFree(map->tab_size);
+    (void)hipFree(map->plan_words);
+    (void)hipFree(map->plan_temp);
     (void)hipHostFree(map->stage);
     (void)hipEventDestroy(map->ev_read);
     delete map;
@@ -1834,9 +1882,168 @@ int rt_sample_map_set_from_adaptive(rt_sample_map* map, uint32_t quantum, void* 
     return sample_map_set(map, a.tiles, quantum, st, info);
 }
 
+// The set call without a host wait: the table never leaves the device. Behind the
+// frames queued on the map (events) the planner (rt_sample_map_plan.hip) clamps, sorts, chooses the
+// unit and writes the order, the clamped counts and the block table; the host keeps the cap. Buffers
+// are allocated here and the block table grows here only (a growth waits for the frames that read
+// the old one: the one host wait this call can contain, at most once per cap and unit).
+// `halves`: the plan of a feedback frame (rt_sample_map_device.h DevicePlanParams::halves; count_cap
+// even). d_tile_counts null: the map's own feedback counts (rt_sample_map::next).
+static int queue_device_plan(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t unit_samples, uint32_t count_cap,
+                             bool halves, hipStream_t st, const char* who) {
+    if (count_cap > rt::sample_map::kMaxCount)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": count_cap = " + std::to_string(count_cap) + " is above 2^19");
+    if (unit_samples > rt::sample_map::kMaxUnit)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
+    if (map->n_tiles > rt::sample_map::kDeviceMaxBlocks)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the band has " + std::to_string(map->n_tiles) +
+                                                 " tiles, more than the 2^22 entries of a device-planned block table");
+    rt_context* ctx = map->ctx;
+    const size_t n = map->n_tiles;
+    auto alloc_fail = [&](hipError_t e) {
+        return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    };
+    if (!map->tab_size) {   // the planner's buffers, once per map
+        size_t temp = 0;
+        if (hipError_t e = rt::device_plan_temp_bytes(map->n_tiles, &temp); e != hipSuccess) return alloc_fail(e);
+        void *rec = nullptr, *words = nullptr, *tmp = nullptr;
+        static_assert(sizeof(rt::TabSize) == 16, "the summary follows the size record, 16-byte aligned");
+        static_assert(sizeof(rt::sample_map::DeviceSummary) % 8 == 0, "the feedback frames' counter follows the summary");
+        const size_t rec_bytes = sizeof(rt::TabSize) + sizeof(rt::sample_map::DeviceSummary) + sizeof(unsigned long long);
+        hipError_t e = hipMalloc(&rec, rec_bytes);
+        if (e == hipSuccess) e = hipMemset(rec, 0, rec_bytes);
+        if (e == hipSuccess) e = hipMalloc(&words, 5u * n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&tmp, temp ? temp : 16u);
+        if (e != hipSuccess) {
+            (void)hipFree(rec);
+            (void)hipFree(words);
+            (void)hipFree(tmp);
+            return alloc_fail(e);
+        }
+        map->tab_size = static_cast<rt::TabSize*>(rec);
+        map->summary = reinterpret_cast<rt::sample_map::DeviceSummary*>(map->tab_size + 1);
+        map->moved = reinterpret_cast<unsigned long long*>(map->summary + 1);
+        map->plan_words = static_cast<uint32_t*>(words);
+        map->next = map->plan_words + 4u * n;
+        map->plan_temp = tmp;
+        map->plan_temp_bytes = temp;
+    }
+    const uint32_t unit0 = rt::sample_map::device_unit0(unit_samples, count_cap);
+    // (halves: the capacity of one half; the buffer holds the two halves and the B half's second copy)
+    const uint64_t natural = std::max<uint64_t>(1u, rt::sample_map::device_capacity(n, halves ? count_cap / 2u : count_cap, unit0));
+    const uint64_t entries = halves ? 3u * natural : natural;
+    if (entries > map->cap_blocks) {
+        rt::BlockEntry* grown = nullptr;
+        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), entries * sizeof(rt::BlockEntry)); e != hipSuccess)
+            return alloc_fail(e);
+        if (map->blocks) {   // frames queued on the map read the old table
+            if (map->read_pending) {
+                ctx->host_waits++;
+                RT_HIP(hipEventSynchronize(map->ev_read));
+            }
+            (void)hipFree(map->blocks);
+        }
+        map->blocks = grown;
+        map->cap_blocks = entries;
+    }
+    // (a test's limit below the non-zero tiles would leave no unit that fits: never below n_tiles)
+    const uint64_t capacity = map->limit_blocks ? std::min(natural, std::max<uint64_t>(map->limit_blocks, n)) : natural;
+    if (int rc = order_on(ctx, st)) return rc;
+    if (map->read_pending) RT_HIP(hipStreamWaitEvent(st, map->ev_read, 0));
+    rt::sample_map::DevicePlanParams K{};
+    K.counts = d_tile_counts ? d_tile_counts : map->next;
+    K.halves = halves ? 1u : 0u;
+    K.n_tiles = map->n_tiles;
+    K.band_w = map->band_w;
+    K.band_h = map->band_h;
+    K.tiles_x = (map->band_w + 7u) / 8u;
+    K.count_cap = count_cap;
+    K.unit0 = unit0;
+    K.capacity = capacity;
+    K.order = map->table;
+    K.clamped = map->table + n;
+    K.blocks = map->blocks;
+    K.summary = map->summary;
+    K.keys = map->plan_words;
+    K.vals = map->plan_words + n;
+    K.keys_sorted = map->plan_words + 2u * n;
+    K.offsets = map->plan_words + 3u * n;
+    K.temp = map->plan_temp;
+    K.temp_bytes = map->plan_temp_bytes;
+    map->set = false;   // until the planner is queued whole
+    if (hipError_t e = rt::launch_device_plan(K, st); e != hipSuccess)
+        return fail(RT_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    RT_HIP(hipEventRecord(map->ev_read, st));   // whoever rewrites the map next waits for the planner too
+    map->read_pending = true;
+    if (int rc = mark_issued(ctx, st)) return rc;
+    map->plan = rt::sample_map::Plan{};
+    map->info = rt_sample_map_info{};
+    map->info.tiles = map->n_tiles;
+    map->schedule = RT_SAMPLE_MAP_ONE_LAUNCH;
+    map->unit_samples = 0;
+    map->n_blocks = 0;
+    map->count_cap = count_cap;
+    map->device_planned = true;
+    map->halves = halves;
+    map->half_capacity = halves ? capacity : 0u;
+    map->set = true;
+    return RT_OK;
+}
+
+int rt_sample_map_set_device_async(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t unit_samples,
+                                   uint32_t count_cap, void* stream) {
+    if (!map || !d_tile_counts) return fail(RT_ERR_INVALID_ARGUMENT, "map or d_tile_counts is NULL");
+    rt::DeviceGuard g(map->ctx->device);
+    return queue_device_plan(map, d_tile_counts, unit_samples, count_cap, false, static_cast<hipStream_t>(stream),
+                             "rt_sample_map_set_device_async");
+}
+
+int rt_sample_map_device_unit(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t count_cap, uint32_t unit_samples,
+                              uint64_t capacity, uint32_t* unit_used) {
+    std::string err;
+    if (int rc = rt::sample_map::device_unit(tile_counts, n_tiles, count_cap, unit_samples, capacity, unit_used, nullptr, &err))
+        return fail(rc, err);
+    return RT_OK;
+}
+
+int rt_sample_map_feedback_count(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, uint32_t min_spp,
+                                 uint32_t max_spp, uint32_t* next) {
+    if (!next) return fail(RT_ERR_INVALID_ARGUMENT, "next is NULL");
+    if (E >= rt::kAdaptiveMaxSum || S >= rt::kAdaptiveMaxSum) return fail(RT_ERR_INVALID_ARGUMENT, "E and S must be below 2^56");
+    if (n > rt::kAdaptiveMaxSpp) return fail(RT_ERR_INVALID_ARGUMENT, "n must be at most 2^19");
+    if (m == 0 || m > 64u) return fail(RT_ERR_INVALID_ARGUMENT, "m must be within 1 .. 64");
+    if (min_spp < 2u || (min_spp & 1u) || (max_spp & 1u) || min_spp > max_spp || max_spp > rt::kAdaptiveMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT, "min_spp and max_spp must be even with 2 <= min_spp <= max_spp <= 2^19");
+    *next = rt::sample_map_feedback_count(E, S, n, m, thr_q16, min_spp, max_spp);
+    return RT_OK;
+}
+
+int rt_debug_hand_out(uint32_t n_units, uint64_t reserve, uint64_t grid_waves, uint32_t* n_block_units,
+                      uint32_t* first_blocks) {
+    if (!n_block_units || !first_blocks) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    const rt::HandOut h = rt::hand_out(n_units, reserve, grid_waves);
+    *n_block_units = h.n_block_units;
+    *first_blocks = h.first_blocks;
+    return RT_OK;
+}
+
+int rt_debug_sample_map_limit_blocks(rt_sample_map* map, uint64_t limit) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    map->limit_blocks = limit;
+    return RT_OK;
+}
+
 int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out) {
     if (!map || !out) return fail(RT_ERR_INVALID_ARGUMENT, "map or out is NULL");
     *out = map->info;
+    if (map->set && map->device_planned) {   // (levels and min_count stay 0: the planner does not count them)
+        rt::DeviceGuard g(map->ctx->device);
+        rt::sample_map::DeviceSummary s;
+        if (int rc = device_summary(map, &s)) return rc;
+        out->max_count = s.max_count;
+        out->samples = s.samples;
+        out->tile_launches = s.live_tiles;
+    }
     return RT_OK;
 }
 
@@ -1860,6 +2067,13 @@ int rt_sample_map_get_schedule(const rt_sample_map* map, uint32_t* schedule, uin
     if (schedule) *schedule = map->schedule;
     if (unit_samples_used) *unit_samples_used = map->unit_samples;
     if (n_blocks) *n_blocks = map->n_blocks;
+    if (map->set && map->device_planned && (unit_samples_used || n_blocks)) {
+        rt::DeviceGuard g(map->ctx->device);
+        rt::sample_map::DeviceSummary s;
+        if (int rc = device_summary(map, &s)) return rc;
+        if (unit_samples_used) *unit_samples_used = s.unit_used;
+        if (n_blocks) *n_blocks = s.n_blocks;
+    }
     return RT_OK;
 }
 
@@ -1875,15 +2089,21 @@ int rt_sample_map_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint
 int rt_debug_sample_map_blocks(const rt_sample_map* map, uint32_t* out, uint64_t capacity, uint64_t* n) {
     if (!map || !n) return fail(RT_ERR_INVALID_ARGUMENT, "map or n is NULL");
     if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: the map was never set");
-    if (out && capacity < map->n_blocks)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: capacity is below the table's " +
-                                                 std::to_string(map->n_blocks) + " blocks");
     rt::DeviceGuard g(map->ctx->device);
-    if (out && map->n_blocks) {
-        if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-        RT_HIP(hipMemcpy(out, map->blocks, map->n_blocks * sizeof(rt::BlockEntry), hipMemcpyDeviceToHost));
+    uint64_t n_blocks = map->n_blocks;
+    if (map->device_planned) {   // the count is the planner's
+        rt::sample_map::DeviceSummary s;
+        if (int rc = device_summary(map, &s)) return rc;
+        n_blocks = std::min<uint64_t>(s.n_blocks, map->cap_blocks);
     }
-    *n = map->n_blocks;
+    if (out && capacity < n_blocks)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: capacity is below the table's " +
+                                                 std::to_string(n_blocks) + " blocks");
+    if (out && n_blocks) {
+        if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+        RT_HIP(hipMemcpy(out, map->blocks, n_blocks * sizeof(rt::BlockEntry), hipMemcpyDeviceToHost));
+    }
+    *n = n_blocks;
     return RT_OK;
 }
 
@@ -1946,7 +2166,10 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
     if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
     const uint32_t cap = rci->samplesPerRenderCall;
-    if (cap < map->info.max_count)
+    if (map->device_planned && cap < map->count_cap)   // the host knows no more of such a map
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
+                                                 " is below the map's count_cap " + std::to_string(map->count_cap));
+    if (!map->device_planned && cap < map->info.max_count)
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
                                                  " is below the map's max_count " + std::to_string(map->info.max_count));
     if (uint64_t(o.sample_base) + cap > 0xffffffffull)
@@ -1972,7 +2195,24 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
     P.head_tiles = 0u;
     // (after a failure between the first launch and the resolve the planes hold partial sums:
     // abort_on_planes)
-    if (map->schedule == RT_SAMPLE_MAP_ONE_LAUNCH) {
+    if (map->device_planned) {
+        // The table's size is device data: the launch takes it from the map's size record, filled on
+        // the stream from the planner's block count (launch_units), and runs on the full persistent
+        // grid, whatever the table holds (an empty one retires every wave at its first refill).
+        P.block_tab = map->blocks;
+        P.tab_size = map->tab_size;
+        P.tile_order = nullptr;
+        P.chunks = P.head_chunks = 1u;
+        P.n_units = 0u;
+        S.tab_blocks = &map->summary->n_blocks;
+        S.plan.lpt = 1u;
+        S.plan.chunks = S.plan.head_chunks = 1u;
+        S.plan.head_tiles = 0u;
+        S.plan.n_units = 0u;
+        rt::launch::hand_out_units(S.in, S.plan, true);
+        S.plan.grid = uint32_t(std::max<uint64_t>(1u, uint64_t(S.in.cu_count) * S.plan.blocks_per_cu));
+        if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
+    } else if (map->schedule == RT_SAMPLE_MAP_ONE_LAUNCH) {
         if (map->n_blocks) {   // (an all-zero map: the resolve alone)
             P.block_tab = map->blocks;
             P.tile_order = nullptr;
@@ -2000,6 +2240,133 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
     RT_HIP(hipEventRecord(map->ev_read, st));   // the next set call waits for this frame
     map->read_pending = true;
     return render_issued(ctx, st);
+}
+
+// A feedback frame: the map's A half into planes A and its B half into planes B
+// (two table launches sized on the device), the update (the next counts from the two halves'
+// difference), the resolve (A + B by the map's counts; zeroes both) and the planner in halves mode
+// on the next counts. Everything is queued; the context orders it behind whatever it queued before,
+// so the one table of the map is rebuilt only after the frames that read it.
+int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                         uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                                         uint32_t* sample_count, const rt_options* opt, rt_sample_map* map,
+                                         const rt_sample_map_feedback* fb, uint64_t* d_tile_error, void* stream) {
+    static const char* const who = "rt_render_sample_map_feedback_device";
+    rt_options o{};
+    bool empty = false;
+    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, &empty)) return rc;
+    if (!map || !fb) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": map or feedback is NULL");
+    if (map->ctx != ctx) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map belongs to another context");
+    if (band_width != map->band_w || band_height != map->band_h)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": band size " + std::to_string(band_width) + " x " +
+                                                 std::to_string(band_height) + " is not the map's " +
+                                                 std::to_string(map->band_w) + " x " + std::to_string(map->band_h));
+    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map was never set");
+    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
+    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
+    const uint32_t cap = rci->samplesPerRenderCall;
+    if (cap & 1u) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) must be even");
+    if (!(std::isfinite(fb->threshold) && fb->threshold >= 0.0f && fb->threshold <= 16.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback threshold must be finite and within [0, 16]");
+    if (fb->min_spp < 2u || (fb->min_spp & 1u) || (fb->max_spp & 1u) || fb->min_spp > fb->max_spp ||
+        fb->max_spp > rt::kAdaptiveMaxSpp)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": feedback min_spp and max_spp must be even with 2 <= min_spp <= max_spp <= 2^19");
+    if (cap < fb->max_spp)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
+                                                 " is below the feedback max_spp " + std::to_string(fb->max_spp));
+    if (fb->unit_samples > rt::sample_map::kMaxUnit)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback unit_samples is above 2^19");
+    if (fb->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback reserved must be 0");
+    const uint32_t held = map->device_planned ? map->count_cap : map->info.max_count;
+    if (cap < held)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
+                                                 " is below the map's " + (map->device_planned ? "count_cap " : "max_count ") +
+                                                 std::to_string(held));
+    if (uint64_t(o.sample_base) + cap > 0xffffffffull)
+        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + samplesPerRenderCall overflows 32 bits");
+    if (map->n_tiles > rt::sample_map::kDeviceMaxBlocks)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the band has more than 2^22 tiles");
+    rt_context::Adaptive& a = ctx->adaptive;
+    if (a.frame.open)
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is open on this context");
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = order_on(ctx, st)) return rc;
+    const size_t n = map->n_tiles;
+    if (!(map->device_planned && map->halves && map->count_cap == cap)) {
+        // the first feedback frame on this map (or at this cap): its current counts, in halves
+        if (int rc = queue_device_plan(map, map->table + n, fb->unit_samples, cap, true, st, who)) return rc;
+    }
+    TraceSetup S;
+    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
+    const uint64_t texels = uint64_t(band_width) * band_height;
+    if (int rc = adaptive_reserve(ctx, texels, S.n_tiles, st)) return rc;
+    rt::TraceParams& P = S.P;
+    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * a.cap_tiles : nullptr;
+    P.tile_order = nullptr;
+    P.accumulate = 0u;
+    P.head_tiles = 0u;
+    P.tab_size = map->tab_size;
+    P.chunks = P.head_chunks = 1u;
+    P.n_units = 0u;
+    S.tab_blocks = &map->summary->half_blocks;
+    S.plan.lpt = 1u;
+    S.plan.chunks = S.plan.head_chunks = 1u;
+    S.plan.head_tiles = 0u;
+    S.plan.n_units = 0u;
+    rt::launch::hand_out_units(S.in, S.plan, true);
+    S.plan.grid = uint32_t(std::max<uint64_t>(1u, uint64_t(S.in.cu_count) * S.plan.blocks_per_cu));
+    unsigned long long* half[2] = {a.planes, a.planes + 3u * texels};
+    for (int h = 0; h < 2; h++) {   // the B half's entries once more from entry 2 x half_capacity
+        P.fixed = half[h];
+        P.block_tab = map->blocks + (h ? 2u * map->half_capacity : 0u);
+        if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
+    }
+    rt::FeedbackParams F{};
+    F.a = half[0];
+    F.b = half[1];
+    F.texels = texels;
+    F.band_w = band_width;
+    F.band_h = band_height;
+    F.tiles_x = P.tiles_x;
+    F.n_tiles = map->n_tiles;
+    F.tile_n = map->table + n;
+    F.thr_q16 = rt::adaptive_thr_q16(fb->threshold);
+    F.min_spp = fb->min_spp;
+    F.max_spp = fb->max_spp;
+    F.next = map->next;
+    F.tile_error = reinterpret_cast<unsigned long long*>(d_tile_error);
+    F.moved = map->moved;
+    if (hipError_t e = rt::launch_feedback_update(F, st); e != hipSuccess)
+        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_feedback_update: ") + hipGetErrorString(e)));
+    if (hipError_t e = rt::launch_adaptive_resolve(half[0], half[1], texels, band_width, P.tiles_x, map->table + n, accum, out,
+                                                   sample_count, st);
+        e != hipSuccess)
+        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
+    if (int rc = render_issued(ctx, st)) return rc;
+    // the next frame's table, from the counts the update chose (<= max_spp <= cap)
+    return queue_device_plan(map, nullptr, fb->unit_samples, cap, true, st, who);
+}
+
+int rt_debug_host_waits(rt_context* ctx, uint64_t* n) {
+    if (!ctx || !n) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    *n = ctx->host_waits;
+    return RT_OK;
+}
+
+int rt_debug_sample_map_feedback(rt_sample_map* map, uint32_t* next, uint64_t* raised, uint64_t* lowered) {
+    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
+    if (!map->next) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_feedback: the map was never planned on the device");
+    rt::DeviceGuard g(map->ctx->device);
+    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
+    unsigned long long moved = 0;
+    RT_HIP(hipMemcpy(&moved, map->moved, sizeof(moved), hipMemcpyDeviceToHost));
+    if (next) RT_HIP(hipMemcpy(next, map->next, size_t(map->n_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (raised) *raised = moved & 0xffffffffull;
+    if (lowered) *lowered = moved >> 32;
+    return RT_OK;
 }
 
 int rt_get_stats(rt_context* ctx, rt_stats* out) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rt_abi.h"
+#include "rt_hand_out.h"
 
 namespace rt {
 
@@ -260,6 +261,10 @@ struct TraceParams {
                                    // launch (rt_big_table_kernel), read through the scalar cache
     const BlockEntry* block_tab;   // optional: the table form (null: the uniform hand-out above). Last, so
                                    // that every other parameter keeps its place in the kernel argument
+    const TabSize* tab_size;       // optional, table form only: n_units, n_block_units and first_blocks
+                                   // come from this device record, read once at kernel entry (a table
+                                   // planned on the device, whose size the host does not know), and
+                                   // the three fields above are unused
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,

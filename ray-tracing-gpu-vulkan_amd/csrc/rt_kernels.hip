@@ -542,6 +542,9 @@ struct WaveBlock {
     uint32_t next = 0, end = 0, tile = 0, s0 = 0, s1 = 0;
     bool dry = false, done = false;
     uint32_t seed = 0;
+    // TAB == 2 kernels: the launch's n_units, n_block_units and first_blocks from the device record
+    // TraceParams::tab_size (first_block); the other kernels read P's
+    uint32_t n_units = 0, n_block_units = 0, first_blocks = 0;
 };
 
 __device__ __forceinline__ void take_block(const rt::TraceParams& P, uint32_t lane, WaveBlock& blk,
@@ -628,7 +631,7 @@ __device__ __forceinline__ void steal_tail(const rt::TraceParams& P, uint32_t la
     }
 }
 
-template <int MODE, bool COUNT, bool TAB = false>
+template <int MODE, bool COUNT, int TAB = 0>
 __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, uint32_t& st, Path& ps,
                                        WaveBlock& blk, Stamps& stamps) {
     if (MODE == rt::MODE_HASH && blk.done) steal_tail<COUNT>(P, lane, st, ps);   // wave-uniform condition
@@ -652,7 +655,7 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
         if (!blk.dry) {
             if (int(lane) == leader) nb = atomicAdd(&P.counters->work_head, 64u);
             nb = __builtin_amdgcn_readfirstlane(__shfl(nb, leader));
-            if (nb >= P.n_block_units) blk.dry = true;
+            if (nb >= (TAB == 2 ? blk.n_block_units : P.n_block_units)) blk.dry = true;
         }
         if (!blk.dry) {
             if (TAB) take_block_tab(P, lane, blk, nb >> 6);
@@ -661,11 +664,12 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
             if (rank >= avail) { u = nb + (rank - avail); t = blk.tile; seed = sn; s0 = blk.s0; s1 = blk.s1; }
             blk.next = nb + rest;
         } else {
-            uint32_t tb = P.n_units;   // exhausted: the lanes retire
+            const uint32_t n_units = TAB == 2 ? blk.n_units : P.n_units;
+            uint32_t tb = n_units;   // exhausted: the lanes retire
             if (!blk.done) {
                 if (int(lane) == leader) tb = atomicAdd(&P.counters->work_tail, rest);
-                tb = P.n_block_units + __shfl(tb, leader);
-                if (tb + rest >= P.n_units) blk.done = true;
+                tb = (TAB == 2 ? blk.n_block_units : P.n_block_units) + __shfl(tb, leader);
+                if (tb + rest >= n_units) blk.done = true;
             }
             if (rank >= avail) { u = tb + (rank - avail); per_lane = true; }
             blk.next = blk.end;
@@ -673,7 +677,7 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
     }
     if (st != ST_NEED_UNIT) return;
     if (per_lane) {
-        if (u >= P.n_units) { st = ST_RETIRED; return; }
+        if (u >= (TAB == 2 ? blk.n_units : P.n_units)) { st = ST_RETIRED; return; }
         const uint32_t b = u >> 6;
         if (TAB) {   // entry u >> 6, per lane
             const rt::BlockEntry e = load_now_block(P.block_tab + b);
@@ -700,10 +704,22 @@ __device__ __forceinline__ void refill(const rt::TraceParams& P, uint32_t lane, 
 // them): 16 Ki waves asking one address at once would queue for ~0.1 ms. Block ranks are dealt
 // across blocks of the grid first (rank = wave-in-block * grid + block), so the longest chains of
 // the LPT order start on different CUs (and XCDs) instead of sharing block 0's SIMDs.
-template <bool TAB = false>
+template <int TAB = 0>
 __device__ __forceinline__ void first_block(const rt::TraceParams& P, uint32_t lane, WaveBlock& blk) {
     const uint32_t wid = (threadIdx.x >> 6) * gridDim.x + blockIdx.x;
-    if (wid < P.first_blocks) {
+    uint32_t first_blocks = P.first_blocks;
+    if (TAB == 2) {
+        // A table planned on the device: the launch's sizes are a 16-byte device
+        // record, written before the launch on its stream, read here once per wave; wave-uniform, to
+        // SGPRs. The grid is the full persistent grid then, whatever the table holds: a wave past
+        // first_blocks starts without a block and asks the counters as any wave does after its first
+        // block, so an empty table (every size 0) retires every lane at its first refill.
+        const rt::BlockEntry z = load_now_block(reinterpret_cast<const rt::BlockEntry*>(P.tab_size));
+        blk.n_units = __builtin_amdgcn_readfirstlane(z.tile);
+        blk.n_block_units = __builtin_amdgcn_readfirstlane(z.s0);
+        first_blocks = blk.first_blocks = __builtin_amdgcn_readfirstlane(z.s1);
+    }
+    if (wid < first_blocks) {
         if (TAB) take_block_tab(P, lane, blk, wid);
         else take_block(P, lane, blk, wid, block_tile(P, wid));
         if (wid < P.isolate_blocks) blk.dry = blk.done = true;   // no work beyond its first block
@@ -987,7 +1003,7 @@ constexpr uint32_t kTraceBlock = RT_TRACE_BLOCK;   // one block per CU shares on
 // Brute-force kernel: one segment per loop iteration for every lane (the sphere loop is
 // wave-uniform, so there is no traversal divergence to manage).
 // ---------------------------------------------------------------------------------------------
-template <bool COUNT, int MODE, bool TAB = false>
+template <bool COUNT, int MODE, int TAB = 0>
 __global__ __launch_bounds__(kBruteBlock, RT_BRUTE_WAVES_PER_SIMD) void rt_trace_brute_kernel(const rt::TraceParams P) {
     const uint32_t lane = lane_id();
     const Camera cam = load_camera(P);
@@ -1809,7 +1825,7 @@ __device__ __forceinline__ void walk(const rt::TraceParams& P, const float4* __r
 // longest walk ends. Stamp slots: 0 loop head, 4 sample start, 5 refill, 6 block fetch, 1 ray
 // setup (big spheres), 2 LBVH walk, 3 shading, 7 other.
 // ---------------------------------------------------------------------------------------------
-template <bool COUNT, int LAYOUT, int MODE, bool REC = false, bool FLAT = false, bool TAB = false>
+template <bool COUNT, int LAYOUT, int MODE, bool REC = false, bool FLAT = false, int TAB = 0>
 __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4* __restrict__ nodes4,
                                           const float4* __restrict__ leaf4,
                                           const uint32_t* __restrict__ leaf_ids,
@@ -1953,7 +1969,7 @@ __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4
 }
 
 // LBVH kernel, tree in global memory (A/B reference: every node and leaf from L2).
-template <bool COUNT, int MODE, bool TAB = false>
+template <bool COUNT, int MODE, int TAB = 0>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_global_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -1972,7 +1988,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // [nodes | leaf spheres | leaf ids]. The geometry + material records read by
 // shading stay in HBM: one random record per hit is an L2 hit (staging them in LDS measured the
 // same), and the LDS they would take fits bigger trees as octant copies.
-template <bool COUNT, uint32_t NOCT, int MODE, bool TAB = false>
+template <bool COUNT, uint32_t NOCT, int MODE, int TAB = 0>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_lds_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -2029,7 +2045,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // FLAT: the grid is one cell thick in y, as every grid of a scene whose small spheres lie in one
 // layer is (configs 3 and 5): the DDA steps x and z only (grid_walk; launch_trace picks it).
 template <bool COUNT, int MODE, bool IN_LDS, bool COOP = false, bool REC = false, bool CQ = false, bool FLAT = false,
-          bool TAB = false>
+          int TAB = 0>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_grid_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -2077,7 +2093,7 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 // LBVH kernel for trees too big for LDS: the treelet (rt_build.hip build_treelet) is staged in LDS
 // with its rank links turned into LDS addresses; leaves, subtrees below the cut, geometry and
 // materials stay in HBM/L2.
-template <bool COUNT, int MODE, bool TAB = false>
+template <bool COUNT, int MODE, int TAB = 0>
 __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_top_kernel(const rt::TraceParams P) {
     UTIL_INIT;
     PLACEMENT_RECORD(P);
@@ -2142,6 +2158,20 @@ __global__ __launch_bounds__(256) void rt_launch_prep_kernel(rt::Counters* __res
         counters->t_dry = ~0ull;
         counters->work_head = work_head;
     }
+}
+
+// The sizes of a table launch whose table was planned on the device (rt_sample_map_plan.hip): from
+// the block count in device memory, the record the trace kernel reads at entry (TraceParams::
+// tab_size) and the work counter past the first blocks, by the host plan's own rule (rt_hand_out.h).
+// One thread, after rt_launch_prep_kernel on the launch's stream. n_blocks <= 2^23 (the planner's
+// capacity, twice in halves mode), so 64 n_blocks fits 32 bits.
+__global__ void rt_tab_size_kernel(const uint32_t* __restrict__ n_blocks, uint32_t reserve, uint32_t grid_waves,
+                                   rt::TabSize* __restrict__ rec, rt::Counters* __restrict__ counters) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t n_units = *n_blocks * 64u;
+    const rt::HandOut h = rt::hand_out(n_units, reserve, grid_waves);
+    *rec = rt::TabSize{n_units, h.n_block_units, h.first_blocks, 0u};
+    counters->work_head = 64u * h.first_blocks;
 }
 
 __global__ __launch_bounds__(256) void rt_resolve_fixed_kernel(unsigned long long* __restrict__ fixed, uint64_t n,
@@ -2259,8 +2289,11 @@ __global__ __launch_bounds__(256) void rt_debug_exact_kernel(uint64_t base, floa
 // ---- host-callable launchers (rt_api.cpp) ---------------------------------------------------
 namespace rt {
 
-// TAB: the table form of the hand-out (TraceParams::block_tab), HASH launches only.
-template <int MODE, bool TAB>
+// TAB: the table form of the hand-out (TraceParams::block_tab), HASH launches only: 1 a table whose
+// size is in the kernel argument, 2 one whose size is a device record (TraceParams::tab_size). Two
+// instantiations, not a branch on P.tab_size: the host-table kernels keep their source (DESIGN.md
+// §3.1.2 measured the one-instantiation form 0.4-1 % slower on them).
+template <int MODE, int TAB>
 static const void* pick_mode(uint32_t accel, bool count, bool flat) {
 #define RT_FN(...) reinterpret_cast<const void*>(__VA_ARGS__)
 #define RT_GRID(C, IN_LDS, COOP, REC, CQ, FLAT) RT_FN(rt_trace_grid_kernel<C, MODE, IN_LDS, COOP, REC, CQ, FLAT, TAB>)
@@ -2302,9 +2335,10 @@ static const void* pick_mode(uint32_t accel, bool count, bool flat) {
 #undef RT_FN
 }
 
-static const void* pick(uint32_t accel, bool count, int mode, bool flat, bool tab = false) {
-    if (mode != MODE_HASH) return pick_mode<MODE_STREAM, false>(accel, count, flat);
-    return tab ? pick_mode<MODE_HASH, true>(accel, count, flat) : pick_mode<MODE_HASH, false>(accel, count, flat);
+static const void* pick(uint32_t accel, bool count, int mode, bool flat, int tab = 0) {
+    if (mode != MODE_HASH) return pick_mode<MODE_STREAM, 0>(accel, count, flat);
+    if (tab == 2) return pick_mode<MODE_HASH, 2>(accel, count, flat);
+    return tab ? pick_mode<MODE_HASH, 1>(accel, count, flat) : pick_mode<MODE_HASH, 0>(accel, count, flat);
 }
 
 bool flat_grid_form(const TraceParams& P, uint32_t accel, bool count) {
@@ -2319,7 +2353,7 @@ hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mo
                         hipStream_t st) {
     void* args[] = {const_cast<TraceParams*>(&P)};
     // (the table form's occupancy is its uniform twin's: the same launch bounds and LDS)
-    return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count), P.block_tab != nullptr), dim3(grid),
+    return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count), P.block_tab ? (P.tab_size ? 2 : 1) : 0), dim3(grid),
                            dim3(block_size(accel)),
                            args, lds_bytes, st);
 }
@@ -2338,6 +2372,14 @@ hipError_t launch_prep(const TraceParams& P, uint32_t work_head, float* tab, uin
     const uint32_t blocks = n_cost > 4096u ? min(64u, (n_cost + 4095u) / 4096u) : 1u;
     hipLaunchKernelGGL(rt_launch_prep_kernel, dim3(blocks), dim3(256), 0, st, P.counters, work_head, P.geom, P.radius,
                        P.big_ids, P.n_big, reinterpret_cast<float4*>(tab), P.tile_cost, n_cost);
+    return hipGetLastError();
+}
+
+hipError_t launch_tab_size(const uint32_t* n_blocks, uint64_t reserve, uint64_t grid_waves, TabSize* rec,
+                           Counters* counters, hipStream_t st) {
+    const uint32_t cap = 0xffffffffu;   // (a reserve or grid beyond 32 bits acts as one of 2^32 - 1: n_units < 2^31)
+    hipLaunchKernelGGL(rt_tab_size_kernel, dim3(1), dim3(64), 0, st, n_blocks, uint32_t(reserve < cap ? reserve : cap),
+                       uint32_t(grid_waves < cap ? grid_waves : cap), rec, counters);
     return hipGetLastError();
 }
 

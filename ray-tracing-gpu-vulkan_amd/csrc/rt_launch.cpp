@@ -307,6 +307,8 @@ int split_units(const Inputs& in, Plan& P, uint32_t spp, uint64_t pixels, uint64
     return 0;
 }
 
+uint64_t refill_reserve(const Inputs& in) { return uint64_t(Tuning::get(in.tune.refill_reserve, 8192)); }
+
 void hand_out_units(const Inputs& in, Plan& P, bool tile_order) {
     const int mode = int(P.mode);
     const uint64_t blk = P.block;
@@ -317,9 +319,10 @@ void hand_out_units(const Inputs& in, Plan& P, bool tile_order) {
     {   // Block hand-out: the last `reserve` units go out one by one. Measured
         // (scripts/refill_ab.py, 1080p): 0 to 32 Ki are within 1 %, one pixel per lane of the
         // grid (262 Ki) is 10-15 % slower at 13-50 spp.
-        const uint64_t reserve = uint64_t(Tuning::get(in.tune.refill_reserve, 8192));
-        P.n_block_units = P.n_units > reserve ? uint32_t((P.n_units - reserve) & ~uint64_t(63)) : 0u;
-        P.first_blocks = uint32_t(std::min<uint64_t>(uint64_t(grid) * blk / 64u, P.n_block_units / 64u));
+        const uint64_t reserve = refill_reserve(in);
+        const rt::HandOut h = rt::hand_out(P.n_units, reserve, uint64_t(grid) * blk / 64u);   // (rt_hand_out.h)
+        P.n_block_units = h.n_block_units;
+        P.first_blocks = h.first_blocks;
         // A STREAM frame is as long as its longest pixel chain; the waves that
         // start on the longest-chain tiles of the LPT order take no further work, so no refill of
         // their other lanes slows the chain down. 1/512 of the waves (32 on a full MI355X):

@@ -153,6 +153,10 @@ int split_units(const Inputs& in, Plan& p, uint32_t spp, uint64_t pixels, uint64
 // entries of a block table, rt_sample_map.h): the grid size and the block hand-out (n_block_units,
 // first_blocks, isolate_blocks; the refill_reserve rule).
 void hand_out_units(const Inputs& in, Plan& p, bool tile_order);
+// The units handed out one by one at the end of the queue (Tuning::refill_reserve or the default);
+// rt::hand_out (rt_hand_out.h) derives n_block_units and first_blocks from it, on the host here and
+// on the device for a table planned there.
+uint64_t refill_reserve(const Inputs& in);
 
 // Both halves for the band of `in` (rt_debug_launch_plan without a context).
 int make_plan(const Inputs& in, const Device& dev, Plan& p, const char** err);

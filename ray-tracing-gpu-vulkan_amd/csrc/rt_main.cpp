@@ -177,8 +177,11 @@ int run_adaptive(uint32_t samples, uint32_t width, uint32_t height, bool store, 
 // The frame loop with adaptive frames, on device 0: frame i is an adaptive frame when
 // i % (replay + 1) == 0, else a sample-map frame replaying the latest adaptive frame's counts. One
 // stream, the scene rebuilt per frame as run_frames does; the replays are queued without a host wait.
+// feedback: frame 0 is the adaptive frame and every later frame a feedback frame:
+// it renders the map, measures it and plans the next frame's map on the device; after the one set call
+// behind frame 0 the host waits for nothing but the end of a report window.
 int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate, bool store,
-                        const rt_adaptive& ad, uint32_t replay, uint32_t map_schedule) {
+                        const rt_adaptive& ad, uint32_t replay, uint32_t map_schedule, bool feedback) {
     rt_context* ctx = nullptr;
     rt_sample_map* map = nullptr;
     hipStream_t stream = nullptr;
@@ -187,7 +190,8 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     CLI_HIP(hipSetDevice(0));
     CLI_RT(rt_context_create(0, &ctx));
     CLI_RT(rt_sample_map_create(ctx, width, height, &map));
-    CLI_RT(rt_sample_map_set_schedule(map, map_schedule, 0));
+    // (a feedback loop's one host-planned map may hold any number of distinct counts)
+    CLI_RT(rt_sample_map_set_schedule(map, feedback ? RT_SAMPLE_MAP_ONE_LAUNCH : map_schedule, 0));
     CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     CLI_HIP(hipMalloc(&accum, size_t(width) * height * 16));
     CLI_HIP(hipMalloc(&rgba8, size_t(width) * height * 4));
@@ -201,6 +205,11 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     bool map_stale = true;   // an adaptive frame has run since the map was set
     rt_sample_map_info map_info;
     std::memset(&map_info, 0, sizeof(map_info));
+    rt_sample_map_feedback fb;
+    std::memset(&fb, 0, sizeof(fb));
+    fb.threshold = ad.threshold;
+    fb.min_spp = ad.min_spp;
+    fb.max_spp = samples;
     const auto t_start = std::chrono::steady_clock::now();
     auto frame = [&]() -> int {
         const float t = animate ? std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() : 0.0f;
@@ -208,7 +217,13 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         RenderCallInfo rci;
         CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
         CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
-        if (frame_index % (uint64_t(replay) + 1u) == 0) {
+        if (feedback && frame_index > 0) {
+            if (map_stale) CLI_RT(rt_sample_map_set_from_adaptive(map, 0, stream, &map_info));
+            map_stale = false;
+            CLI_RT(rt_render_sample_map_feedback_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, map,
+                                                        &fb, nullptr, stream));
+            ++window_replays;
+        } else if (frame_index % (uint64_t(replay) + 1u) == 0) {
             rt_adaptive_info info;
             CLI_RT(rt_render_adaptive_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, &ad, &info,
                                              stream));
@@ -243,6 +258,13 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         CLI_HIP(hipStreamSynchronize(stream));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
         done += k;
+        if (feedback) {   // (the stream is idle: the info call's wait costs nothing)
+            if (window_replays) CLI_RT(rt_sample_map_get_info(map, &map_info));
+            std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u feedback frames, next map mean %.2f spp "
+                        "of at most %u)\n",
+                        sec / k * 1e3, k, double(ad.threshold), window_replays, double(map_info.samples) / pixels, samples);
+            continue;
+        }
         std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u replays, map launch %s, mean %.2f spp "
                     "of at most %u, %.1f Msamples/s)\n",
                     sec / k * 1e3, k, double(ad.threshold), window_replays,
@@ -287,7 +309,7 @@ int main(int argc, const char** argv) {
     uint32_t samples = 10, width = 1920, height = 1080, gpu_count = 1, frames = 0, rng_mode = RT_RNG_PIXEL_STREAM;
     uint32_t replay = 0, map_schedule = RT_SAMPLE_MAP_LEVELS;
     bool rng_explicit = false, replay_given = false, map_launch_given = false;
-    bool store = false, animate = false, adaptive = false;
+    bool store = false, animate = false, adaptive = false, feedback = false;
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
@@ -308,6 +330,9 @@ int main(int argc, const char** argv) {
             std::puts("                                  # frames replay its per-tile sample counts (no pass loop)");
             std::puts("--map-launch <levels|one>         # With --replay: a launch per distinct count (default) or one");
             std::puts("                                  # launch of a block table per replayed frame");
+            std::puts("--feedback                        # With --adaptive and --frames: every frame after the first renders");
+            std::puts("                                  # the previous frame's map, measures its noise and plans the next");
+            std::puts("                                  # map on the GPU (not with --replay)");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -318,6 +343,8 @@ int main(int argc, const char** argv) {
             adaptive = true;
         } else if (a == "--store") {
             store = true;
+        } else if (a == "--feedback") {
+            feedback = true;
         } else if (a == "--animate") {
             animate = true;
         } else if (a == "--rng") {
@@ -356,6 +383,14 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "--replay needs --adaptive and --frames\n");
         return 2;
     }
+    if (feedback && !(adaptive && frames > 0)) {
+        std::fprintf(stderr, "--feedback needs --adaptive and --frames\n");
+        return 2;
+    }
+    if (feedback && replay_given) {
+        std::fprintf(stderr, "--feedback plans every frame's map itself: it cannot run with --replay\n");
+        return 2;
+    }
     if (map_launch_given && !replay_given) {
         std::fprintf(stderr, "--map-launch needs --replay (with --adaptive and --frames)\n");
         return 2;
@@ -375,7 +410,7 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
-    if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay, map_schedule);
+    if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay, map_schedule, feedback);
     if (adaptive) return run_adaptive(samples, width, height, store, ad);
     if (frames > 0) return run_frames(samples, width, height, gpu_count, frames, animate, store, rng_mode);
     // ray_trace() keeps the reference's signature; its stream is selected through RT_RNG. An

@@ -177,5 +177,27 @@ int block_plan_arrays(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t qu
     return RT_OK;
 }
 
+int device_unit(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t count_cap, uint32_t unit_samples,
+                uint64_t capacity, uint32_t* unit_used, uint64_t* n_blocks, std::string* err) {
+    if (n_tiles != 0 && !tile_counts) return refuse(err, "tile_counts is NULL");
+    if (count_cap > kMaxCount) return refuse(err, "count_cap = " + std::to_string(count_cap) + " is above 2^19");
+    if (unit_samples > kMaxUnit)
+        return refuse(err, "unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
+    const uint32_t unit0 = device_unit0(unit_samples, count_cap);
+    uint64_t blocks = 0;
+    for (uint32_t j = 0; j < kDeviceUnitSteps; j++) {
+        const uint64_t unit = device_unit_step(unit0, j);
+        blocks = 0;
+        for (uint32_t t = 0; t < n_tiles; t++) blocks += (std::min<uint64_t>(tile_counts[t], count_cap) + unit - 1u) / unit;
+        if (blocks <= capacity) {
+            if (unit_used) *unit_used = uint32_t(unit);
+            if (n_blocks) *n_blocks = blocks;
+            return RT_OK;
+        }
+    }
+    return refuse(err, "the table has " + std::to_string(blocks) + " non-zero tiles, more than the capacity " +
+                           std::to_string(capacity) + ": no unit fits");
+}
+
 }  // namespace sample_map
 }  // namespace rt

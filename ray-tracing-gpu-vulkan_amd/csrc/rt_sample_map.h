@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
+#include "rt_sample_map_device.h"
 
 namespace rt {
 namespace sample_map {
@@ -91,6 +92,15 @@ int make_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quan
 int block_plan_arrays(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t unit_samples,
                       uint32_t* blocks_out, uint64_t capacity, uint64_t* n_blocks, uint32_t* unit_samples_used,
                       std::string* err);
+
+// ---- maps planned on the device (rt_sample_map_set_device_async, rt_sample_map_plan.hip) ---------
+// The unit the device planner chooses for a table (rt_sample_map_device.h): the smallest U0 2^j, held
+// at 2^19, whose block table of the counts clamped to count_cap has at most `capacity` entries; the
+// table is then make_block_plan's of the clamped counts at that unit. Refusals
+// (RT_ERR_INVALID_ARGUMENT, nothing written): a NULL table, a cap or unit above 2^19, more non-zero
+// tiles than the capacity (no unit fits).
+int device_unit(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t count_cap, uint32_t unit_samples,
+                uint64_t capacity, uint32_t* unit_used, uint64_t* n_blocks, std::string* err);
 
 }  // namespace sample_map
 }  // namespace rt

@@ -30,6 +30,7 @@ __all__ = [
     "load_library", "HASH", "STREAM", "multi_plan", "launch_inputs", "launch_plan", "row_weights", "struct_dict", "partition_strips", "partition_rebalance",
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
+    "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -80,6 +81,15 @@ def make_adaptive(threshold: float, min_spp: int = 8, step_spp: int = 8) -> Adap
     a = Adaptive()
     a.min_spp, a.step_spp, a.threshold, a.reserved = min_spp, step_spp, threshold, 0
     return a
+
+
+def make_feedback(threshold: float, min_spp: int = 4, max_spp: int = 64, unit_samples: int = 0) -> "abi.SampleMapFeedback":
+    """rt_sample_map_feedback of a feedback frame (Renderer.render_sample_map_feedback): a tile that
+    misses `threshold` doubles its count up to max_spp, one that meets half of it halves down to
+    min_spp. Counts are even, 0 <= threshold <= 16."""
+    f = abi.SampleMapFeedback()
+    f.threshold, f.min_spp, f.max_spp, f.unit_samples, f.reserved = threshold, min_spp, max_spp, unit_samples, 0
+    return f
 
 
 def threshold_q16(threshold: float) -> int:
@@ -305,6 +315,48 @@ class Renderer:
                                                     smap._map if smap is not None else None,
                                                     _stream_ptr(stream, self.device)))
 
+    def render_sample_map_feedback(self, rci: RenderCallInfo, accum, out, smap: "SampleMap", feedback, sample_count=None,
+                                   rows=None, options: Optional[Options] = None, tile_error=None, stream=None) -> None:
+        """A feedback frame (rt_render_sample_map_feedback_device): smap's counts (rounded up to even)
+        render as two halves, each tile's next count follows from their difference by `feedback`
+        (make_feedback) and the map is re-planned with those counts on the device; nothing is read
+        back. Tensors as render_sample_map; tile_error: optional contiguous int64 cuda tensor
+        [tiles, 2] receiving (E, S) per tile. rci.samplesPerRenderCall is the cap: even, >=
+        feedback.max_spp and what the map holds."""
+        bh, bw = int(accum.shape[0]), int(accum.shape[1])
+        _check_dev_tensor(accum, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        rows_ptr = None
+        if rows is not None:
+            if rows.numel() != bh or not rows.is_cuda or rows.element_size() != 4 or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous 4-byte cuda tensor of band_h entries")
+            rows_ptr = rows.data_ptr()
+        count_ptr = None
+        if sample_count is not None:
+            if not sample_count.is_cuda or sample_count.element_size() != 4 or sample_count.is_floating_point() \
+                    or not sample_count.is_contiguous() or tuple(sample_count.shape) != (bh, bw):
+                raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            count_ptr = sample_count.data_ptr()
+        err_ptr = None
+        if tile_error is not None:
+            tiles = ((bw + 7) // 8) * ((bh + 7) // 8)
+            if not tile_error.is_cuda or tile_error.element_size() != 8 or tile_error.is_floating_point() \
+                    or not tile_error.is_contiguous() or tile_error.numel() != 2 * tiles:
+                raise ValueError(f"tile_error must be a contiguous 8-byte integer cuda tensor of 2 x {tiles} entries")
+            err_ptr = tile_error.data_ptr()
+        check(self._lib.rt_render_sample_map_feedback_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
+                                                             accum.data_ptr(), out.data_ptr(), count_ptr,
+                                                             ctypes.byref(options) if options is not None else None,
+                                                             smap._map if smap is not None else None,
+                                                             ctypes.byref(feedback) if feedback is not None else None,
+                                                             err_ptr, _stream_ptr(stream, self.device)))
+
+    def host_waits(self) -> int:
+        """Host waits inside calls documented as queued without one (rt_debug_host_waits)."""
+        v = ctypes.c_uint64()
+        check(self._lib.rt_debug_host_waits(self._ctx, ctypes.byref(v)))
+        return int(v.value)
+
     def stats(self) -> Stats:
         st = Stats()
         check(self._lib.rt_get_stats(self._ctx, ctypes.byref(st)))
@@ -469,6 +521,31 @@ class SampleMap:
                                                         ctypes.byref(info)))
         return info
 
+    def set_async(self, tile_counts, unit: int = 0, count_cap: int = 1 << 19, stream=None) -> None:
+        """The set call without a host wait (rt_sample_map_set_device_async): tile_counts as in set(),
+        clamped to count_cap and planned on the device behind the frames queued on the map, under the
+        one-launch schedule with units of `unit` samples (0: automatic from count_cap), doubled until
+        the table fits the map's block capacity. The map is device-planned afterwards: frames need
+        samplesPerRenderCall >= count_cap; info, schedule_info and debug_blocks wait for the planner."""
+        n = self.tiles_x * self.tiles_y
+        if not tile_counts.is_cuda or tile_counts.element_size() != 4 or tile_counts.is_floating_point() \
+                or not tile_counts.is_contiguous() or tile_counts.numel() != n:
+            raise ValueError(f"tile_counts must be a contiguous 4-byte integer cuda tensor of {n} entries")
+        check(self._lib.rt_sample_map_set_device_async(self._map, tile_counts.data_ptr(), unit, count_cap,
+                                                       _stream_ptr(stream, self.renderer.device)))
+
+    def debug_feedback(self) -> dict:
+        """What the map's feedback frames left on the device (rt_debug_sample_map_feedback): {next:
+        the counts the last frame's update chose, raised, lowered: tiles moved over all frames}."""
+        nxt = np.zeros(self.tiles_x * self.tiles_y, np.uint32)
+        up, down = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(self._lib.rt_debug_sample_map_feedback(self._map, nxt.ctypes.data, ctypes.byref(up), ctypes.byref(down)))
+        return {"next": nxt, "raised": up.value, "lowered": down.value}
+
+    def debug_limit_blocks(self, limit: int) -> None:
+        """Tests: set_async plans for at most max(limit, tiles) table entries (0: the map's capacity)."""
+        check(self._lib.rt_debug_sample_map_limit_blocks(self._map, limit))
+
     @property
     def info(self) -> abi.SampleMapInfo:
         info = abi.SampleMapInfo()
@@ -525,6 +602,39 @@ def sample_map_block_plan(counts, quantum: int = 0, unit_samples: int = 0) -> di
     check(lib.rt_sample_map_block_plan(c.ctypes.data if n else None, n, quantum, unit_samples,
                                        blocks.ctypes.data if nb.value else None, nb.value, None, None))
     return {"blocks": blocks, "unit_samples": used.value}
+
+
+def sample_map_device_capacity(n_tiles: int, count_cap: int, unit: int = 0) -> int:
+    """Entries of the block table a device-planned map of n_tiles tiles is allocated for
+    (csrc/rt_sample_map_device.h device_capacity), restated: min(tiles x ceil(cap / U0), 2^22)."""
+    u0 = unit or min(128, max(32, count_cap // 32))
+    return min(n_tiles * max(1, -(-count_cap // u0)), 1 << 22)
+
+
+def sample_map_device_unit(counts, count_cap: int, unit: int = 0, capacity: int | None = None) -> int:
+    """The unit the device planner chooses for the host table `counts` (rt_sample_map_device_unit; host
+    only). capacity None: the capacity of a map of len(counts) tiles."""
+    c = np.ascontiguousarray(np.asarray(counts).reshape(-1), np.uint32)
+    if capacity is None:
+        capacity = sample_map_device_capacity(len(c), count_cap, unit)
+    used = ctypes.c_uint32(0)
+    check(load_library().rt_sample_map_device_unit(c.ctypes.data if len(c) else None, len(c), count_cap, unit, capacity,
+                                                   ctypes.byref(used)))
+    return used.value
+
+
+def sample_map_feedback_count(E: int, S: int, n: int, m: int, thr_q16: int, min_spp: int, max_spp: int) -> int:
+    """The next count of a tile under the feedback rule (rt_sample_map_feedback_count; host only)."""
+    nxt = ctypes.c_uint32(0)
+    check(load_library().rt_sample_map_feedback_count(E, S, n, m, thr_q16, min_spp, max_spp, ctypes.byref(nxt)))
+    return nxt.value
+
+
+def hand_out(n_units: int, reserve: int, grid_waves: int) -> tuple[int, int]:
+    """(n_block_units, first_blocks) of a launch of n_units units (rt_debug_hand_out; host only)."""
+    nbu, fb = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    check(load_library().rt_debug_hand_out(n_units, reserve, grid_waves, ctypes.byref(nbu), ctypes.byref(fb)))
+    return nbu.value, fb.value
 
 
 def sample_map_plan(counts, quantum: int = 0) -> dict:

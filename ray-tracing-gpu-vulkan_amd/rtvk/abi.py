@@ -112,6 +112,12 @@ class SampleMapInfo(ctypes.Structure):
                 ("max_count", ctypes.c_uint32), ("samples", ctypes.c_uint64), ("tile_launches", ctypes.c_uint64)]
 
 
+class SampleMapFeedback(ctypes.Structure):
+    """rt_sample_map_feedback (include/rt_mi355x.h)."""
+    _fields_ = [("threshold", ctypes.c_float), ("min_spp", ctypes.c_uint32), ("max_spp", ctypes.c_uint32),
+                ("unit_samples", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
                "unit_min_samples", "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule", "refill_reserve",
                "isolate_tiles", "sah_knobs")
@@ -191,6 +197,15 @@ EXPORTS = {
     "rt_sample_map_block_plan": (_I, [_P, _U32, _U32, _U32, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U32)]),
     "rt_debug_sample_map_blocks": (_I, [_P, _P, _U64, ctypes.POINTER(_U64)]),
     "rt_debug_sample_map_info": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(SampleMapInfo)]),
+    "rt_sample_map_set_device_async": (_I, [_P, _P, _U32, _U32, _P]),
+    "rt_sample_map_device_unit": (_I, [_P, _U32, _U32, _U32, _U64, ctypes.POINTER(_U32)]),
+    "rt_sample_map_feedback_count": (_I, [_U64, _U64, _U32, _U32, _U32, _U32, _U32, ctypes.POINTER(_U32)]),
+    "rt_debug_sample_map_limit_blocks": (_I, [_P, _U64]),
+    "rt_render_sample_map_feedback_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
+                                                  ctypes.POINTER(Options), _P, ctypes.POINTER(SampleMapFeedback), _P, _P]),
+    "rt_debug_host_waits": (_I, [_P, ctypes.POINTER(_U64)]),
+    "rt_debug_sample_map_feedback": (_I, [_P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    "rt_debug_hand_out": (_I, [_U32, _U64, _U64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     "rt_get_stats": (_I, [_P, ctypes.POINTER(Stats)]),
     "rt_launch_ms": (_I, [_P, _U32, ctypes.POINTER(ctypes.c_float)]),
     "rt_launch_row_weights": (_I, [_P, _U32, _P, _U32]),
