@@ -9,6 +9,7 @@
 #include "rt_adaptive.h"
 #include "rt_device_math.h"
 #include "rt_internal.h"
+#include "rt_launchers.h"
 #include "rt_sample_map_feedback.h"
 
 using namespace rtd;

@@ -3,7 +3,10 @@
 // Replaces the reference's host orchestration for the hot path (src/ray_trace.cpp:42-972,
 // src/vulkan.h): device contexts instead of Vulkan devices, one HBM-resident scene + LBVH per
 // context instead of UBO + BLAS/TLAS, one fused persistent kernel launch per band instead of
-// clear + vkCmdTraceRaysKHR. The multi-device frame (RCCL) and ray_trace() are in rt_multi.cpp.
+// clear + vkCmdTraceRaysKHR. Here: the context's life cycle, scene builds, the plain frame
+// (rt_render_device) with the launch steps every frame kind shares (rt_context.h), statistics and
+// the debug readers. Adaptive frames are in rt_adaptive_frame.cpp, sample maps and their frames in
+// rt_sample_map_frame.cpp, the multi-device frame (RCCL) and ray_trace() in rt_multi.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,7 +16,6 @@
 #include <cstring>
 #include <exception>
 #include <memory>
-#include <new>
 #include <random>
 #include <string>
 #include <utility>
@@ -22,243 +24,12 @@
 #include "../../include/rt_abi.h"
 #include "../../include/rt_mi355x.h"
 #include "../../include/rt_mi355x_debug.h"
-#include "rt_adaptive.h"
-#include "rt_build.h"
 #include "rt_bvh.h"
+#include "rt_context.h"
 #include "rt_grid.h"
-#include "rt_host.h"
-#include "rt_internal.h"
-#include "rt_launch.h"
-#include "rt_sample_map.h"
-#include "rt_sample_map_feedback.h"
-
-namespace rt {
-hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
-                        hipStream_t st);
-hipError_t trace_occupancy(uint32_t accel, bool count, int mode, bool flat, size_t lds_bytes, int* blocks_per_cu);
-bool flat_grid_form(const TraceParams& P, uint32_t accel, bool count);
-hipError_t launch_resolve_fixed(unsigned long long* fixed, uint64_t n_texels, uint32_t accumulate, uint32_t spp,
-                                float* accum, uint8_t* out, hipStream_t st);
-hipError_t launch_tonemap(const float* accum, uint64_t n_texels, uint32_t spp, uint8_t* out, hipStream_t st);
-hipError_t launch_prep(const TraceParams& P, uint32_t work_head, float* tab, uint32_t n_cost, hipStream_t st);
-hipError_t launch_tab_size(const uint32_t* n_blocks, uint64_t reserve, uint64_t grid_waves, TabSize* rec,
-                           Counters* counters, hipStream_t st);
-// rt_sample_map_plan.hip
-hipError_t device_plan_temp_bytes(uint32_t n_tiles, size_t* bytes);
-hipError_t launch_device_plan(const sample_map::DevicePlanParams& K, hipStream_t st);
-uint32_t block_size(uint32_t accel);
-hipError_t launch_scatter_rows(const float* src_acc, const uint8_t* src_px, const uint32_t* rows,
-                               uint32_t n_rows, uint32_t width, uint32_t dst_rows, float* dst_acc, uint8_t* dst_px,
-                               hipStream_t st);
-hipError_t launch_gather_rows(const float* src_acc, const uint32_t* rows, uint32_t n_rows, uint32_t width,
-                              uint32_t src_rows, float* dst_acc, hipStream_t st);
-hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st);
-hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st);
-// rt_adaptive.hip
-hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st);
-hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);
-hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
-                                   uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
-                                   uint32_t* sample_count, hipStream_t st);
-hipError_t launch_feedback_update(const FeedbackParams& K, hipStream_t st);
-hipError_t launch_adaptive_store_tiles(const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
-                                       const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out,
-                                       uint32_t* sample_count, hipStream_t st);
-}  // namespace rt
+#include "rt_launchers.h"
 
 using rt::launch::Tuning;
-
-// One arena of device-built scenes (rt_context::slot; rt_api.cpp device_build_begin).
-struct SceneSlot {
-    rt::DeviceScene scene;            // its arrays (pointers into mem / grid_mem) and counts
-    void* mem = nullptr;              // every per-sphere array of the build, one allocation
-    uint32_t cap_n = 0;               // spheres it holds
-    void* grid_mem = nullptr;         // cell offsets, fill cursor, references, ids, scan scratch
-    size_t grid_cap = 0;              // bytes
-    hipEvent_t ev_free = nullptr;     // recorded after every launch that reads this arena
-    bool used = false;                // ev_free has been recorded
-};
-
-namespace {
-// The launch parameters rt_render_device and rt_render_adaptive_device share: everything that
-// does not depend on how the band's samples are split into units.
-struct TraceSetup {
-    rt::TraceParams P;
-    rt::launch::Inputs in;       // what the plan is computed from
-    rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
-    uint64_t tiles_x = 0, n_tiles = 0;
-    const uint32_t* tab_blocks = nullptr;   // with P.tab_size: the device word that holds the table's block count
-};
-}  // namespace
-
-struct rt_context {
-    int device = 0;
-    Tuning tune;
-    int cu_count = 0;
-    rt::DeviceScene scene;                       // the current scene (host blob or an arena)
-    bool scene_set = false;                      // a set/refit call has succeeded (RT_ERR_NO_SCENE)
-    // device-built scenes: two arenas used alternately, built on the context's own stream
-    SceneSlot slot[2];
-    int slot_cur = -1;                           // arena of the current scene (-1: host-built / none)
-    hipStream_t build_stream = nullptr;
-    hipEvent_t ev_summary = nullptr;             // the build's summary has reached pinned memory
-    hipEvent_t ev_caller = nullptr;              // device spheres: the caller's stream reached the call
-    rt::BuildSummary* summary = nullptr;         // pinned
-    void* sph_stage = nullptr;                   // pinned staging of host spheres
-    size_t sph_stage_cap = 0;
-    bool pending = false;                        // a build begun, not yet ended (rt_multi_set_scene)
-    int pending_slot = 0;
-    uint32_t pending_count = 0;
-    bool refused = false;                        // device_build_end refused non-finite device spheres:
-                                                 // the scene call leaves the previous scene in place
-    rt::Counters* counters = nullptr;            // device
-    float* big_tab = nullptr;                    // device, in the counters' allocation (TraceParams::big_tab)
-    // Every device operation of a context (scene upload / build, render) is ordered after the
-    // previous one, whatever streams they are issued on: an op on a stream other than the last
-    // one first waits for `ev_last`, and every op records it when issued. A device build runs on
-    // the build stream beside the previous op (it waits only for the launches that read its
-    // arena), so it does not cover that op: the op's event moves to `ev_prev`,
-    // which the next op waits for as well (order_on) until an op issued after both clears it.
-    hipStream_t last_stream = nullptr;
-    hipEvent_t ev_last = nullptr;
-    bool ev_valid = false;
-    hipStream_t prev_stream = nullptr;
-    hipEvent_t ev_prev = nullptr;
-    bool prev_valid = false;
-    // the build workspace (ws) holds the topology of a full build that completed: a refit may
-    // reuse it (a full build that failed after overwriting ws leaves it false)
-    bool topo_ok = false;
-    bool pending_refit = false;
-    // occupancy cache per kernel form, count flag and rng mode, valid for occ_lds bytes
-    int occ[rt::ACCEL_COUNT][3][2] = {};   // [form][plain, count_tests, one-layer grid walk][mode]
-    size_t occ_lds[rt::ACCEL_COUNT][3][2] = {};
-    bool has_grid = false;                       // the scene has a grid
-    float grid_pad_radius = 0.0f;                // camera radius the grid's margin covers
-    // unpadded LBVH node boxes (host) and the radius the device copy is padded for
-    std::vector<rt::BvhNode> nodes_host;
-    float scene_radius = 0.0f;
-    float pad_radius = 0.0f;
-    float padded_for = 0.0f;                     // pad radius the device node copy currently carries
-    bool gpu_tree = false;
-    bool treelet_stale = true;                   // ACCEL_LBVH_TOP: the treelet predates the node boxes
-    rt::TileSchedule sched;                      // unit hand-out order (LPT from the last launch's costs)
-    rt::BuildWorkspace ws;                       // device build scratch, kept for refits
-    Sphere* d_spheres = nullptr;                 // staging copy of host-provided spheres (device build)
-    uint32_t d_spheres_cap = 0;
-    // Host-built scenes: every device array lives in one device blob, rewritten in stream order
-    // by one copy from a pinned staging buffer (two, alternating, each guarded by the event of
-    // its last copy), so rt_set_scene builds the next frame's tree on the host while the
-    // previous frame still renders (no device-wide sync, no per-frame hipMalloc/hipFree).
-    void* blob = nullptr;
-    size_t blob_cap = 0;
-    void* stage[2] = {nullptr, nullptr};
-    size_t stage_cap[2] = {0, 0};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    bool stage_used[2] = {false, false};
-    int stage_cur = 0;
-    // RT_RNG_SAMPLE_HASH: 3 planes of fixed-point sums, zero between launches (the resolve
-    // kernel clears what it reads)
-    unsigned long long* fixed = nullptr;
-    uint64_t fixed_cap = 0;                      // texels
-    // the last launch's plan (rt_launch.h; accel 0 = none yet) and what it was computed from, with
-    // the occupancies it queried (rt_debug_launch_info, rt_debug_launch_plan)
-    rt::launch::Plan last_plan;
-    rt::launch::Inputs last_in;
-    // every colour the shaders can return lies in [0, 1] (RT_RNG_SAMPLE_HASH's fixed point needs it)
-    bool colours_unit = true;
-    // host waits inside render and set calls that are documented as queued without one (buffer
-    // growth; rt_debug_host_waits: the feedback tests read 0 once the buffers stand)
-    uint64_t host_waits = 0;
-    // HIP events bracketing the trace kernel of the last kKernelEvents launches (ring; timing
-    // inside a caller's timed region without a host sync per launch, rt_debug_kernel_times)
-    static constexpr uint32_t kKernelEvents = 64;
-    hipEvent_t kev[kKernelEvents][2] = {};
-    uint64_t kev_count = 0;                      // launches recorded so far
-    // Host copies of the last launches' tile-cost records (and the LPT order they ran in), copied
-    // after the kernel on the launch stream: the cross-device balancer reads a launch's per-row
-    // work from them two frames later without a wait on queued work (rt_launch_row_weights).
-    struct CostSnap {
-        uint32_t* host = nullptr;                // pinned: cost[n], then order[n] when has_order
-        uint32_t cap = 0;                        // tiles it holds
-        hipEvent_t ev = nullptr;                 // after the copies
-        bool pending = false;
-        uint64_t launch = ~0ull;                 // launch index the record belongs to
-        uint32_t n = 0, tiles_x = 0, band_h = 0, head_tiles = 0, head_chunks = 1, chunks = 1;
-        bool has_order = false;
-    };
-    static constexpr uint32_t kSnaps = 4;
-    CostSnap snap[kSnaps];
-    bool keep_snaps = false;   // set by the first rt_launch_row_weights (or rt_multi at N > 1):
-                               // a one-device frame loop pays no copies it never reads
-    // Adaptive frames (rt_render_adaptive_device) keep their own buffers, so they
-    // leave `fixed` and `sched` alone.
-    struct Adaptive {
-        unsigned long long* planes = nullptr;   // half-buffers A then B, 3 planes of the band's texels
-                                                // each; zero between calls (the resolve clears them)
-        uint64_t cap = 0;                       // texels the allocation holds (x 6 planes)
-        uint32_t* tiles = nullptr;              // per tile: sample count, the two tile lists and the
-        uint64_t cap_tiles = 0;                 // walk kernels' cost scratch: 4 x cap_tiles words
-        rt::AdaptiveState* state = nullptr;     // device
-        rt::AdaptiveState* host = nullptr;      // pinned copy, read after `ev` once per pass
-        hipEvent_t ev = nullptr;
-        // the band of the last completed adaptive frame, whose count table the head of `tiles` still
-        // holds (0 x 0: none): rt_sample_map_set_from_adaptive reads it
-        uint32_t last_w = 0, last_h = 0;
-        // The frame in flight, between rt::adaptive_begin and rt::adaptive_finish / adaptive_abort
-        // (rt_host.h): the pass loop as a state machine, so that one host thread can interleave
-        // the passes of several contexts (rt_multi_render_adaptive).
-        struct Frame {
-            bool open = false;
-            bool pending = false;               // a pass is issued and its readback not yet consumed
-            TraceSetup S;
-            rt_options o{};
-            rt_adaptive ad{};
-            hipStream_t st = nullptr;
-            uint32_t max_spp = 0, done = 0, passes = 0, cur = 0;
-            uint64_t active = 0;                // tiles of the next pass
-            const uint32_t* list = nullptr;     // their list (null: pass 0, every tile, row-major)
-        } frame;
-    } adaptive;
-};
-
-// A sample map: the plan of its last set call on the host (rt_sample_map.h) and,
-// on the device, what the launches and the resolve read. Rewritten only by a set call, which first
-// waits for `ev_read`, recorded behind every frame that renders the map.
-struct rt_sample_map {
-    rt_context* ctx = nullptr;
-    uint32_t band_w = 0, band_h = 0, n_tiles = 0;
-    uint32_t* table = nullptr;           // device: order[n_tiles], then the quantised counts[n_tiles]
-    uint32_t* stage = nullptr;           // pinned, 2 x n_tiles words: the set calls' copies
-    bool set = false;
-    rt::sample_map::Plan plan;
-    rt_sample_map_info info{};
-    // the schedule the next set call plans by (rt_sample_map_set_schedule), and the one the held plan has
-    uint32_t next_schedule = RT_SAMPLE_MAP_LEVELS, next_unit = 0;
-    uint32_t schedule = RT_SAMPLE_MAP_LEVELS, unit_samples = 0;
-    rt::BlockEntry* blocks = nullptr;    // device: the block table of a one-launch plan (n_blocks entries)
-    uint64_t n_blocks = 0, cap_blocks = 0;
-    hipEvent_t ev_read = nullptr;
-    mutable bool read_pending = false;   // ev_read has been recorded since the last set call
-    // A map planned on the device (rt_sample_map_set_device_async): `table` and `blocks` were written
-    // there, in stream order, and the host knows the cap alone; what the planner found (block count,
-    // unit, totals) stays in `summary` until an info call copies it back. The planner's buffers are
-    // allocated by the first such call.
-    bool device_planned = false;
-    uint32_t count_cap = 0;
-    uint64_t limit_blocks = 0;           // rt_debug_sample_map_limit_blocks (0: none)
-    rt::TabSize* tab_size = nullptr;     // device: the size record of the map's launches, then ...
-    rt::sample_map::DeviceSummary* summary = nullptr;   // ... the planner's summary (one allocation)
-    uint32_t* plan_words = nullptr;      // device: keys, values, sorted keys, offsets (4 x n_tiles)
-    void* plan_temp = nullptr;           // device: the sort's and the scan's scratch
-    size_t plan_temp_bytes = 0;
-    // Feedback frames (rt_render_sample_map_feedback_device): the table is planned in halves mode, one
-    // half of at most half_capacity entries; `next` holds the counts the last frame's update chose
-    // (in plan_words), `moved` the tiles the updates raised | lowered << 32 (behind the summary).
-    bool halves = false;
-    uint64_t half_capacity = 0;
-    uint32_t* next = nullptr;
-    unsigned long long* moved = nullptr;
-};
 
 namespace {
 // Node boxes grow by 12u * R (u = 2^-24): the one-fma slab form of the walk differs from the
@@ -315,21 +86,7 @@ void make_octant_orders(const std::vector<rt::BvhNode>& n, std::vector<rt::BvhNo
     }
 }
 
-// Stream chaining of a context's device operations (rt_context::ev_last).
-int order_on(rt_context* ctx, hipStream_t st) {
-    if (ctx->ev_valid && ctx->last_stream != st) RT_HIP(hipStreamWaitEvent(st, ctx->ev_last, 0));
-    if (ctx->prev_valid && ctx->prev_stream != st) RT_HIP(hipStreamWaitEvent(st, ctx->ev_prev, 0));
-    return RT_OK;
-}
-// After an op issued on `st` behind order_on(ctx, st): it follows everything before it.
-int mark_issued(rt_context* ctx, hipStream_t st) {
-    if (!ctx->ev_last) RT_HIP(hipEventCreateWithFlags(&ctx->ev_last, hipEventDisableTiming));
-    RT_HIP(hipEventRecord(ctx->ev_last, st));
-    ctx->ev_valid = true;
-    ctx->last_stream = st;
-    ctx->prev_valid = false;
-    return RT_OK;
-}
+// Stream chaining (rt_context::ev_last; order_on and mark_issued are below, in namespace rt).
 // After a device build on the build stream, which did not wait for the previous op: the build's
 // event becomes ev_last and the previous op's event is kept in ev_prev (unless the previous op
 // was itself a build, whose own ev_prev then still stands).
@@ -358,17 +115,6 @@ int read_counters(rt_context* ctx, rt::Counters* c) {
     if (int rc = sync_issued(ctx)) return rc;
     RT_HIP(hipMemcpy(c, ctx->counters, sizeof(*c), hipMemcpyDeviceToHost));
     return RT_OK;
-}
-
-// The end of a render call on `st`: the next build into the current scene's arena waits for its
-// launches, and the call becomes the context's last operation.
-int render_issued(rt_context* ctx, hipStream_t st) {
-    if (ctx->slot_cur >= 0) {
-        SceneSlot& sl = ctx->slot[ctx->slot_cur];
-        RT_HIP(hipEventRecord(sl.ev_free, st));
-        sl.used = true;
-    }
-    return mark_issued(ctx, st);
 }
 
 // One device blob for a host-built scene (rt_context::blob): add() the arrays, then commit()
@@ -507,6 +253,37 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+int fail_hip(hipError_t e, const std::string& who) {
+    return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE, who + ": " + hipGetErrorString(e));
+}
+
+// Stream chaining of a context's device operations (rt_context::ev_last).
+int order_on(rt_context* ctx, hipStream_t st) {
+    if (ctx->ev_valid && ctx->last_stream != st) RT_HIP(hipStreamWaitEvent(st, ctx->ev_last, 0));
+    if (ctx->prev_valid && ctx->prev_stream != st) RT_HIP(hipStreamWaitEvent(st, ctx->ev_prev, 0));
+    return RT_OK;
+}
+// After an op issued on `st` behind order_on(ctx, st): it follows everything before it.
+int mark_issued(rt_context* ctx, hipStream_t st) {
+    if (!ctx->ev_last) RT_HIP(hipEventCreateWithFlags(&ctx->ev_last, hipEventDisableTiming));
+    RT_HIP(hipEventRecord(ctx->ev_last, st));
+    ctx->ev_valid = true;
+    ctx->last_stream = st;
+    ctx->prev_valid = false;
+    return RT_OK;
+}
+
+// The end of a render call on `st`: the next build into the current scene's arena waits for its
+// launches, and the call becomes the context's last operation.
+int render_issued(rt_context* ctx, hipStream_t st) {
+    if (ctx->slot_cur >= 0) {
+        SceneSlot& sl = ctx->slot[ctx->slot_cur];
+        RT_HIP(hipEventRecord(sl.ev_free, st));
+        sl.used = true;
+    }
+    return mark_issued(ctx, st);
+}
+
 int refuse_nonfinite(uint32_t index) {
     return fail(RT_ERR_INVALID_ARGUMENT, "sphere " + std::to_string(index) +
                                              ": centre or radius is not finite (NaN or inf); the scene is refused");
@@ -525,6 +302,8 @@ int current_device_count(int* n) {
 using rt::fail;
 using rt::refuse_nonfinite;
 using rt::DeviceGuard;
+using rt::order_on, rt::mark_issued, rt::render_issued, rt::check_render_args, rt::fill_trace, rt::launch_units,
+    rt::grow_on_stream;
 
 extern "C" {
 
@@ -882,9 +661,7 @@ int device_build_begin(rt_context* ctx, const Sphere* spheres, uint32_t count, b
         RT_HIP(hipMemcpyAsync(d.big_ids, ctx->slot[ctx->slot_cur].scene.big_ids, 64 * 4, hipMemcpyDeviceToDevice, bs));
     const rt::BuildOutputs o{d.geom, d.radius, d.mat, d.big_ids, d.nodes, d.nodes_raw, d.leaf_geom, d.leaf_ids};
     const hipError_t e = rt::build_scene_gpu(ctx->ws, ctx->d_spheres, count, o, refit, bs, ctx->summary);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE,
-                    std::string("device LBVH build: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return rt::fail_hip(e, "device LBVH build");
     RT_HIP(hipEventRecord(ctx->ev_summary, bs));
     ctx->pending = true;
     ctx->pending_slot = k;
@@ -1145,6 +922,11 @@ void scene_inputs(const rt_context* ctx, rt::launch::Inputs& in) {
     in.tune = ctx->tune;
 }
 
+}  // namespace
+
+// The steps of a render call that every frame kind takes (rt_context.h).
+namespace rt {
+
 // Argument checks of a render call `who`, before any device work; o = *opt or zeros. *empty: a
 // band without texels, nothing to render.
 int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t band_width, uint32_t band_height,
@@ -1337,332 +1119,6 @@ int launch_tile_prefix(rt_context* ctx, TraceSetup& S, uint32_t spp, uint32_t sa
     return launch_units(ctx, S, st);
 }
 
-// The recovery of a frame on the adaptive planes that failed with `rc` after its first launch: the
-// planes are zero between calls, whatever happened. Keeps the first error and its message.
-int abort_on_planes(rt_context* ctx, hipStream_t st, int rc) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    const std::string msg = rt::g_last_error;
-    (void)hipMemsetAsync(a.planes, 0, a.cap * 6u * sizeof(unsigned long long), st);
-    rt::g_last_error = msg;
-    if (int rc2 = render_issued(ctx, st)) return rc ? rc : rc2;
-    return rc;
-}
-
-// Grows a device buffer that work queued on `st` may still read to `count` units of `unit` bytes
-// (sum planes: zeroed on `st`). An old buffer is freed after the stream has drained (every earlier
-// op of ctx is ordered before it); the new buffer and its capacity are set after success only
-// (a failed growth leaves none).
-template <class T>
-int grow_on_stream(T*& buf, uint64_t& cap, uint64_t count, size_t unit, bool zero, hipStream_t st) {
-    if (buf) {
-        RT_HIP(hipStreamSynchronize(st));
-        RT_HIP(hipFree(buf));
-    }
-    buf = nullptr;
-    cap = 0;
-    void* p = nullptr;
-    RT_HIP(hipMalloc(&p, count * unit));
-    if (zero) RT_HIP(hipMemsetAsync(p, 0, count * unit, st));
-    buf = static_cast<T*>(p);
-    cap = count;
-    return RT_OK;
-}
-
-// Buffers of an adaptive frame of `texels` texels in `n_tiles` tiles.
-int adaptive_reserve(rt_context* ctx, uint64_t texels, uint64_t n_tiles, hipStream_t st) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    if (a.cap < texels) {
-        if (a.planes) ctx->host_waits++;
-        if (int rc = grow_on_stream(a.planes, a.cap, texels, 6u * sizeof(unsigned long long), true, st)) return rc;
-    }
-    if (a.cap_tiles < n_tiles) {
-        a.last_w = a.last_h = 0;   // the last frame's count table goes with the old buffer
-        if (int rc = grow_on_stream(a.tiles, a.cap_tiles, n_tiles, 4u * sizeof(uint32_t), false, st)) return rc;
-    }
-    if (!a.state) RT_HIP(hipMalloc(reinterpret_cast<void**>(&a.state), sizeof(rt::AdaptiveState)));
-    if (!a.host) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&a.host), sizeof(rt::AdaptiveState), hipHostMallocDefault));
-    if (!a.ev) RT_HIP(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
-    return RT_OK;
-}
-
-// The half-buffers and tile tables of the frame in flight.
-struct AdaptiveBuffers {
-    uint64_t texels, n_tiles;
-    unsigned long long* half[2];
-    uint32_t* tile_n;
-    uint32_t* lists[2];
-};
-AdaptiveBuffers adaptive_buffers(rt_context* ctx) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    const rt::TraceParams& P = a.frame.S.P;
-    AdaptiveBuffers b;
-    b.texels = uint64_t(P.band_w) * P.band_h;
-    b.n_tiles = a.frame.S.n_tiles;
-    b.half[0] = a.planes;
-    b.half[1] = a.planes + 3u * b.texels;
-    b.tile_n = a.tiles;
-    b.lists[0] = a.tiles + b.n_tiles;
-    b.lists[1] = a.tiles + 2u * b.n_tiles;
-    return b;
-}
-
-// The set calls of a sample map, the one synchronous step: waits for the frames
-// that read the map, brings the count table `d_counts` (written by earlier work on `st`) to the
-// host, plans it there and uploads the order and the quantised table, under the one-launch schedule
-// the block table too (into a buffer of its own, grown before anything of the map changes). A
-// refusal leaves the map as it was.
-int sample_map_set(rt_sample_map* map, const uint32_t* d_counts, uint32_t quantum, hipStream_t st,
-                   rt_sample_map_info* info) {
-    const size_t n = map->n_tiles;
-    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-    map->read_pending = false;
-    RT_HIP(hipMemcpyAsync(map->stage, d_counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipStreamSynchronize(st));
-    rt::sample_map::Plan plan;
-    rt::sample_map::BlockPlan bp;
-    rt_sample_map_info fresh{};
-    std::string err;
-    const bool one = map->next_schedule == RT_SAMPLE_MAP_ONE_LAUNCH;
-    if (one) {
-        if (int rc = rt::sample_map::make_block_plan(map->stage, map->n_tiles, quantum, map->next_unit, bp, &err))
-            return fail(rc, err);
-        plan = std::move(bp.plan);
-    } else if (int rc = rt::sample_map::make_plan(map->stage, map->n_tiles, quantum, plan, &err)) {
-        return fail(rc, err);
-    }
-    if (int rc = rt::sample_map::totals(plan, map->band_w, map->band_h, &fresh, &err)) return fail(rc, err);
-    if (one) fresh.tile_launches = bp.live_tiles;   // every non-zero tile is launched once
-    rt::BlockEntry* grown = nullptr;
-    if (one && bp.blocks.size() > map->cap_blocks) {
-        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), bp.blocks.size() * sizeof(rt::BlockEntry)); e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE,
-                        std::string("rt_sample_map block table: ") + hipGetErrorString(e));
-    }
-    std::copy(plan.order.begin(), plan.order.end(), map->stage);
-    std::copy(plan.quantised.begin(), plan.quantised.end(), map->stage + n);
-    map->set = false;   // until the upload has landed
-    if (grown) {   // (no frame reads the old table: ev_read was waited for above)
-        (void)hipFree(map->blocks);
-        map->blocks = grown;
-        map->cap_blocks = bp.blocks.size();
-    }
-    map->n_blocks = 0;
-    RT_HIP(hipMemcpyAsync(map->table, map->stage, 2u * n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (one && !bp.blocks.empty())
-        RT_HIP(hipMemcpyAsync(map->blocks, bp.blocks.data(), bp.blocks.size() * sizeof(rt::BlockEntry),
-                              hipMemcpyHostToDevice, st));
-    RT_HIP(hipStreamSynchronize(st));   // frames on any stream of the context may follow
-    map->plan = std::move(plan);
-    map->info = fresh;
-    map->schedule = map->next_schedule;
-    map->unit_samples = one ? bp.unit_samples : 0u;
-    map->n_blocks = one ? bp.blocks.size() : 0u;
-    map->set = true;
-    map->device_planned = false;
-    map->halves = false;
-    if (info) *info = fresh;
-    return RT_OK;
-}
-
-// The planner's summary of a device-planned map, after a host wait for the planner (and whatever was
-// queued on the map since): the one synchronisation such a map has, in the info calls only.
-int device_summary(const rt_sample_map* map, rt::sample_map::DeviceSummary* s) {
-    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-    RT_HIP(hipMemcpy(s, map->summary, sizeof(*s), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-}  // namespace
-
-// The adaptive pass loop as steps on a context (rt_host.h).
-namespace rt {
-
-int adaptive_check_values(const RenderCallInfo* rci, const rt_options& o, const rt_adaptive* ad, const char* who) {
-    if (!ad) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive is NULL");
-    const uint32_t max_spp = rci->samplesPerRenderCall;
-    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
-    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
-    if (ad->min_spp == 0 || (ad->min_spp & 1u)) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp must be even and >= 2");
-    if (ad->step_spp == 0 || (ad->step_spp & 1u))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive step_spp must be even and >= 2");
-    if (max_spp == 0 || (max_spp & 1u))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive max_spp (samplesPerRenderCall) must be even and >= 2");
-    if (ad->min_spp > max_spp) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive min_spp exceeds max_spp (samplesPerRenderCall)");
-    if (uint64_t(o.sample_base) + max_spp > 0xffffffffull)
-        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + max_spp overflows 32 bits");
-    if (!(std::isfinite(ad->threshold) && ad->threshold >= 0.0f && ad->threshold <= 16.0f))
-        return fail(RT_ERR_INVALID_ARGUMENT, "adaptive threshold must be finite and within [0, 16]");
-    if (ad->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive reserved must be 0");
-    return RT_OK;
-}
-
-int adaptive_check(const rt_context* ctx, const RenderCallInfo* rci, uint32_t band_width, uint32_t band_height,
-                   const float* accum, const uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
-                   const char* who, rt_options* o_out, bool* empty) {
-    rt_options o;
-    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, empty)) return rc;
-    if (*empty) return RT_OK;
-    if (int rc = adaptive_check_values(rci, o, ad, who)) return rc;
-    if (o_out) *o_out = o;
-    return RT_OK;
-}
-
-int adaptive_abort(rt_context* ctx, int rc) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    if (!a.frame.open) return rc;
-    DeviceGuard g(ctx->device);
-    a.frame.open = a.frame.pending = false;
-    return abort_on_planes(ctx, a.frame.st, rc);
-}
-
-int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
-                   uint32_t band_height, float* accum, uint8_t* out, const rt_options* opt, const rt_adaptive* ad,
-                   void* stream, const char* who, bool* open) {
-    *open = false;
-    rt_options o;
-    bool empty = false;
-    if (int rc = adaptive_check(ctx, rci, band_width, band_height, accum, out, opt, ad, who, &o, &empty)) return rc;
-    if (empty) return RT_OK;
-    rt_context::Adaptive& a = ctx->adaptive;
-    rt_context::Adaptive::Frame& f = a.frame;
-    if (f.open) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is in flight on this context");
-    DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;
-    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, f.S)) return rc;
-    if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, f.S.n_tiles, st)) return rc;
-    rt::TraceParams& P = f.S.P;
-    // the walk kernels record tile costs unconditionally (rt_kernels.hip record_tile_cost): a
-    // scratch table of the whole tile grid, never read
-    P.tile_cost = f.S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * f.S.n_tiles : nullptr;
-    P.accumulate = 0u;
-    P.head_tiles = 0u;
-    f.o = o;
-    f.ad = *ad;
-    f.st = st;
-    f.max_spp = rci->samplesPerRenderCall;
-    f.done = f.passes = f.cur = 0;
-    f.active = f.S.n_tiles;
-    f.list = nullptr;   // pass 0: every tile, row-major
-    f.pending = false;
-    f.open = true;      // from here on a failure leaves sums or state behind: adaptive_abort clears them
-    a.last_w = a.last_h = 0;   // the passes overwrite the last frame's count table
-    if (hipError_t e = rt::launch_adaptive_init(a.state, st); e != hipSuccess)
-        return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_init: ") + hipGetErrorString(e)));
-    *open = true;
-    return RT_OK;
-}
-
-bool adaptive_active(const rt_context* ctx) { return ctx->adaptive.frame.open && ctx->adaptive.frame.active != 0; }
-
-int adaptive_issue_pass(rt_context* ctx) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    rt_context::Adaptive::Frame& f = a.frame;
-    if (!f.open || f.pending || !f.active) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive pass out of order");
-    DeviceGuard g(ctx->device);
-    const AdaptiveBuffers b = adaptive_buffers(ctx);
-    TraceSetup& S = f.S;
-    rt::TraceParams& P = S.P;
-    hipStream_t st = f.st;
-    const uint32_t k = f.passes == 0 ? f.ad.min_spp : std::min(f.ad.step_spp, f.max_spp - f.done);
-    for (uint32_t h = 0; h < 2; h++) {   // samples [done, done + k/2) into A, the next k/2 into B
-        P.fixed = b.half[h];
-        P.tile_order = f.list;
-        if (int rc = launch_tile_prefix(ctx, S, k / 2u, f.o.sample_base + f.done + h * (k / 2u), f.active,
-                                        f.list != nullptr, st))
-            return rc;
-    }
-    f.done += k;
-    rt::AdaptiveErrorParams K;
-    std::memset(&K, 0, sizeof(K));
-    K.a = b.half[0];
-    K.b = b.half[1];
-    K.texels = b.texels;
-    K.band_w = P.band_w;
-    K.band_h = P.band_h;
-    K.tiles_x = P.tiles_x;
-    K.list = f.list;
-    K.n_list = uint32_t(f.active);
-    K.n_done = f.done;
-    K.max_spp = f.max_spp;
-    K.thr_q16 = rt::adaptive_thr_q16(f.ad.threshold);
-    K.cur = f.cur;
-    K.tile_n = b.tile_n;
-    K.next_list = b.lists[f.cur ^ 1u];
-    K.state = a.state;
-    RT_HIP(rt::launch_adaptive_error(K, st));
-    // the one readback of the pass: the next list's length (and the running totals)
-    RT_HIP(hipMemcpyAsync(a.host, a.state, sizeof(rt::AdaptiveState), hipMemcpyDeviceToHost, st));
-    RT_HIP(hipEventRecord(a.ev, st));
-    f.pending = true;
-    return RT_OK;
-}
-
-int adaptive_pass_done(rt_context* ctx, bool block, bool* done) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    rt_context::Adaptive::Frame& f = a.frame;
-    if (done) *done = false;
-    if (!f.open || !f.pending) return fail(RT_ERR_INVALID_ARGUMENT, "no adaptive pass in flight");
-    DeviceGuard g(ctx->device);
-    if (block) {
-        RT_HIP(hipEventSynchronize(a.ev));
-    } else {
-        const hipError_t e = hipEventQuery(a.ev);
-        if (e == hipErrorNotReady) {
-            (void)hipGetLastError();   // not an error: nothing for a later launch check to pick up
-            return RT_OK;
-        }
-        RT_HIP(e);
-    }
-    const AdaptiveBuffers b = adaptive_buffers(ctx);
-    f.pending = false;
-    f.passes++;
-    f.cur ^= 1u;
-    f.active = a.host->count[f.cur];
-    f.list = b.lists[f.cur];
-    if (f.active > b.n_tiles) return fail(RT_ERR_DEVICE, "adaptive tile list longer than the tile grid");
-    if (done) *done = true;
-    return RT_OK;
-}
-
-int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info) {
-    rt_context::Adaptive& a = ctx->adaptive;
-    rt_context::Adaptive::Frame& f = a.frame;
-    if (!f.open || f.pending || f.active) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive finish out of order");
-    DeviceGuard g(ctx->device);
-    const AdaptiveBuffers b = adaptive_buffers(ctx);
-    const rt::TraceParams& P = f.S.P;
-    if (hipError_t e = rt::launch_adaptive_resolve(b.half[0], b.half[1], b.texels, P.band_w, P.tiles_x, b.tile_n, accum,
-                                                   out, sample_count, f.st);
-        e != hipSuccess)
-        return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
-    if (info) {
-        info->passes = f.passes;
-        info->tiles = uint32_t(b.n_tiles);
-        info->tiles_capped = a.host->capped;
-        info->reserved = 0;
-        info->samples = a.host->samples;
-    }
-    f.open = false;
-    a.last_w = P.band_w;
-    a.last_h = P.band_h;
-    return render_issued(ctx, f.st);
-}
-
-const uint32_t* adaptive_tile_counts(const rt_context* ctx) { return ctx->adaptive.tiles; }
-
-int adaptive_store_tiles(int device, const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
-                         const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out, uint32_t* sample_count,
-                         void* stream) {
-    if (n_rows == 0 || width == 0) return RT_OK;
-    if (!src || !tile_n || !rows || !accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    DeviceGuard g(device);
-    RT_HIP(rt::launch_adaptive_store_tiles(src, n_rows, width, tile_n, rows, dst_rows, accum, out, sample_count,
-                                           static_cast<hipStream_t>(stream)));
-    return RT_OK;
-}
-
 }  // namespace rt
 
 extern "C" {
@@ -1777,595 +1233,9 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
     return render_issued(ctx, st);
 }
 
-int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
-                              uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
-                              uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
-                              rt_adaptive_info* info, void* stream) {
-    if (info) std::memset(info, 0, sizeof(*info));
-    // the state machine of rt_host.h, one context: each pass waits for its own readback
-    bool open = false;
-    if (int rc = rt::adaptive_begin(ctx, rci, rows, band_width, band_height, accum, out, opt, ad, stream,
-                                    "rt_render_adaptive_device", &open))
-        return rc;
-    if (!open) return RT_OK;   // a band without texels
-    int rc = RT_OK;
-    while (rc == RT_OK && rt::adaptive_active(ctx)) {
-        rc = rt::adaptive_issue_pass(ctx);
-        if (rc == RT_OK) rc = rt::adaptive_pass_done(ctx, true, nullptr);
-    }
-    if (rc != RT_OK) return rt::adaptive_abort(ctx, rc);
-    return rt::adaptive_finish(ctx, accum, out, sample_count, info);
-}
-
-int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, int* converged) {
-    if (!converged) return fail(RT_ERR_INVALID_ARGUMENT, "converged is NULL");
-    if (E >= rt::kAdaptiveMaxSum || S >= rt::kAdaptiveMaxSum)
-        return fail(RT_ERR_INVALID_ARGUMENT, "E and S must be below 2^56");
-    if (n > rt::kAdaptiveMaxSpp) return fail(RT_ERR_INVALID_ARGUMENT, "n above 2^19");
-    if (m == 0 || m > 64u) return fail(RT_ERR_INVALID_ARGUMENT, "m must be within 1 .. 64");
-    *converged = rt::adaptive_tile_converged(E, S, n, m, thr_q16) ? 1 : 0;
-    return RT_OK;
-}
-
-// ---- sample-map frames ------------------------------------------------------
-int rt_sample_map_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_sample_map** out) {
-    if (!ctx || !out) return fail(RT_ERR_INVALID_ARGUMENT, "ctx or out is NULL");
-    *out = nullptr;
-    if (band_width == 0 || band_height == 0 || band_width > 65535u || band_height > 65535u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be within 1 .. 65535");
-    const uint64_t n_tiles = uint64_t((band_width + 7u) / 8u) * ((band_height + 7u) / 8u);
-    if (n_tiles >= (1ull << 26)) return fail(RT_ERR_INVALID_ARGUMENT, "band too large");
-    rt::DeviceGuard g(ctx->device);
-    std::unique_ptr<rt_sample_map> m(new (std::nothrow) rt_sample_map);
-    if (!m) return fail(RT_ERR_OUT_OF_MEMORY, "rt_sample_map_create: out of host memory");
-    m->ctx = ctx;
-    m->band_w = band_width;
-    m->band_h = band_height;
-    m->n_tiles = uint32_t(n_tiles);
-    m->info.tiles = m->n_tiles;
-    auto cleanup = [&](int rc) {
-        if (m->table) (void)hipFree(m->table);
-        if (m->stage) (void)hipHostFree(m->stage);
-        if (m->ev_read) (void)hipEventDestroy(m->ev_read);
-        return rc;
-    };
-    const size_t bytes = size_t(n_tiles) * 2u * sizeof(uint32_t);
-    if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->table), bytes); e != hipSuccess)
-        return cleanup(fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE,
-                            std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
-    if (hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&m->stage), bytes, hipHostMallocDefault); e != hipSuccess)
-        return cleanup(fail(RT_ERR_OUT_OF_MEMORY, std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
-    if (hipError_t e = hipEventCreateWithFlags(&m->ev_read, hipEventDisableTiming); e != hipSuccess)
-        return cleanup(fail(RT_ERR_DEVICE, std::string("rt_sample_map_create: ") + hipGetErrorString(e)));
-    *out = m.release();
-    return RT_OK;
-}
-
-int rt_sample_map_destroy(rt_sample_map* map) {
-    if (!map) return RT_OK;
-    rt::DeviceGuard g(map->ctx->device);
-    if (map->read_pending) (void)hipEventSynchronize(map->ev_read);   // the frames that read it
-    (void)hipFree(map->table);
-    (void)hipFree(map->blocks);
-    (void)hipFree(map->tab_size);
-    (void)hipFree(map->plan_words);
-    (void)hipFree(map->plan_temp);
-    (void)hipHostFree(map->stage);
-    (void)hipEventDestroy(map->ev_read);
-    delete map;
-    return RT_OK;
-}
-
-int rt_sample_map_set_device(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t quantum, void* stream,
-                             rt_sample_map_info* info) {
-    if (!map || !d_tile_counts) return fail(RT_ERR_INVALID_ARGUMENT, "map or d_tile_counts is NULL");
-    rt::DeviceGuard g(map->ctx->device);
-    return sample_map_set(map, d_tile_counts, quantum, static_cast<hipStream_t>(stream), info);
-}
-
-int rt_sample_map_set_from_adaptive(rt_sample_map* map, uint32_t quantum, void* stream, rt_sample_map_info* info) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    rt_context* ctx = map->ctx;
-    const rt_context::Adaptive& a = ctx->adaptive;
-    if (a.frame.open)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_from_adaptive: an adaptive frame is open on this context");
-    if (a.last_w == 0 || !a.tiles)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_from_adaptive: the context has no completed adaptive frame");
-    if (a.last_w != map->band_w || a.last_h != map->band_h)
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "rt_sample_map_set_from_adaptive: the last adaptive frame's band size " + std::to_string(a.last_w) +
-                        " x " + std::to_string(a.last_h) + " is not the map's " + std::to_string(map->band_w) + " x " +
-                        std::to_string(map->band_h));
-    rt::DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;   // behind the adaptive frame, whatever stream it ran on
-    return sample_map_set(map, a.tiles, quantum, st, info);
-}
-
-// The set call without a host wait: the table never leaves the device. Behind the
-// frames queued on the map (events) the planner (rt_sample_map_plan.hip) clamps, sorts, chooses the
-// unit and writes the order, the clamped counts and the block table; the host keeps the cap. Buffers
-// are allocated here and the block table grows here only (a growth waits for the frames that read
-// the old one: the one host wait this call can contain, at most once per cap and unit).
-// `halves`: the plan of a feedback frame (rt_sample_map_device.h DevicePlanParams::halves; count_cap
-// even). d_tile_counts null: the map's own feedback counts (rt_sample_map::next).
-static int queue_device_plan(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t unit_samples, uint32_t count_cap,
-                             bool halves, hipStream_t st, const char* who) {
-    if (count_cap > rt::sample_map::kMaxCount)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": count_cap = " + std::to_string(count_cap) + " is above 2^19");
-    if (unit_samples > rt::sample_map::kMaxUnit)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
-    if (map->n_tiles > rt::sample_map::kDeviceMaxBlocks)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the band has " + std::to_string(map->n_tiles) +
-                                                 " tiles, more than the 2^22 entries of a device-planned block table");
-    rt_context* ctx = map->ctx;
-    const size_t n = map->n_tiles;
-    auto alloc_fail = [&](hipError_t e) {
-        return fail(e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    };
-    if (!map->tab_size) {   // the planner's buffers, once per map
-        size_t temp = 0;
-        if (hipError_t e = rt::device_plan_temp_bytes(map->n_tiles, &temp); e != hipSuccess) return alloc_fail(e);
-        void *rec = nullptr, *words = nullptr, *tmp = nullptr;
-        static_assert(sizeof(rt::TabSize) == 16, "the summary follows the size record, 16-byte aligned");
-        static_assert(sizeof(rt::sample_map::DeviceSummary) % 8 == 0, "the feedback frames' counter follows the summary");
-        const size_t rec_bytes = sizeof(rt::TabSize) + sizeof(rt::sample_map::DeviceSummary) + sizeof(unsigned long long);
-        hipError_t e = hipMalloc(&rec, rec_bytes);
-        if (e == hipSuccess) e = hipMemset(rec, 0, rec_bytes);
-        if (e == hipSuccess) e = hipMalloc(&words, 5u * n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&tmp, temp ? temp : 16u);
-        if (e != hipSuccess) {
-            (void)hipFree(rec);
-            (void)hipFree(words);
-            (void)hipFree(tmp);
-            return alloc_fail(e);
-        }
-        map->tab_size = static_cast<rt::TabSize*>(rec);
-        map->summary = reinterpret_cast<rt::sample_map::DeviceSummary*>(map->tab_size + 1);
-        map->moved = reinterpret_cast<unsigned long long*>(map->summary + 1);
-        map->plan_words = static_cast<uint32_t*>(words);
-        map->next = map->plan_words + 4u * n;
-        map->plan_temp = tmp;
-        map->plan_temp_bytes = temp;
-    }
-    const uint32_t unit0 = rt::sample_map::device_unit0(unit_samples, count_cap);
-    // (halves: the capacity of one half; the buffer holds the two halves and the B half's second copy)
-    const uint64_t natural = std::max<uint64_t>(1u, rt::sample_map::device_capacity(n, halves ? count_cap / 2u : count_cap, unit0));
-    const uint64_t entries = halves ? 3u * natural : natural;
-    if (entries > map->cap_blocks) {
-        rt::BlockEntry* grown = nullptr;
-        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&grown), entries * sizeof(rt::BlockEntry)); e != hipSuccess)
-            return alloc_fail(e);
-        if (map->blocks) {   // frames queued on the map read the old table
-            if (map->read_pending) {
-                ctx->host_waits++;
-                RT_HIP(hipEventSynchronize(map->ev_read));
-            }
-            (void)hipFree(map->blocks);
-        }
-        map->blocks = grown;
-        map->cap_blocks = entries;
-    }
-    // (a test's limit below the non-zero tiles would leave no unit that fits: never below n_tiles)
-    const uint64_t capacity = map->limit_blocks ? std::min(natural, std::max<uint64_t>(map->limit_blocks, n)) : natural;
-    if (int rc = order_on(ctx, st)) return rc;
-    if (map->read_pending) RT_HIP(hipStreamWaitEvent(st, map->ev_read, 0));
-    rt::sample_map::DevicePlanParams K{};
-    K.counts = d_tile_counts ? d_tile_counts : map->next;
-    K.halves = halves ? 1u : 0u;
-    K.n_tiles = map->n_tiles;
-    K.band_w = map->band_w;
-    K.band_h = map->band_h;
-    K.tiles_x = (map->band_w + 7u) / 8u;
-    K.count_cap = count_cap;
-    K.unit0 = unit0;
-    K.capacity = capacity;
-    K.order = map->table;
-    K.clamped = map->table + n;
-    K.blocks = map->blocks;
-    K.summary = map->summary;
-    K.keys = map->plan_words;
-    K.vals = map->plan_words + n;
-    K.keys_sorted = map->plan_words + 2u * n;
-    K.offsets = map->plan_words + 3u * n;
-    K.temp = map->plan_temp;
-    K.temp_bytes = map->plan_temp_bytes;
-    map->set = false;   // until the planner is queued whole
-    if (hipError_t e = rt::launch_device_plan(K, st); e != hipSuccess)
-        return fail(RT_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    RT_HIP(hipEventRecord(map->ev_read, st));   // whoever rewrites the map next waits for the planner too
-    map->read_pending = true;
-    if (int rc = mark_issued(ctx, st)) return rc;
-    map->plan = rt::sample_map::Plan{};
-    map->info = rt_sample_map_info{};
-    map->info.tiles = map->n_tiles;
-    map->schedule = RT_SAMPLE_MAP_ONE_LAUNCH;
-    map->unit_samples = 0;
-    map->n_blocks = 0;
-    map->count_cap = count_cap;
-    map->device_planned = true;
-    map->halves = halves;
-    map->half_capacity = halves ? capacity : 0u;
-    map->set = true;
-    return RT_OK;
-}
-
-int rt_sample_map_set_device_async(rt_sample_map* map, const uint32_t* d_tile_counts, uint32_t unit_samples,
-                                   uint32_t count_cap, void* stream) {
-    if (!map || !d_tile_counts) return fail(RT_ERR_INVALID_ARGUMENT, "map or d_tile_counts is NULL");
-    rt::DeviceGuard g(map->ctx->device);
-    return queue_device_plan(map, d_tile_counts, unit_samples, count_cap, false, static_cast<hipStream_t>(stream),
-                             "rt_sample_map_set_device_async");
-}
-
-int rt_sample_map_device_unit(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t count_cap, uint32_t unit_samples,
-                              uint64_t capacity, uint32_t* unit_used) {
-    std::string err;
-    if (int rc = rt::sample_map::device_unit(tile_counts, n_tiles, count_cap, unit_samples, capacity, unit_used, nullptr, &err))
-        return fail(rc, err);
-    return RT_OK;
-}
-
-int rt_sample_map_feedback_count(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, uint32_t min_spp,
-                                 uint32_t max_spp, uint32_t* next) {
-    if (!next) return fail(RT_ERR_INVALID_ARGUMENT, "next is NULL");
-    if (E >= rt::kAdaptiveMaxSum || S >= rt::kAdaptiveMaxSum) return fail(RT_ERR_INVALID_ARGUMENT, "E and S must be below 2^56");
-    if (n > rt::kAdaptiveMaxSpp) return fail(RT_ERR_INVALID_ARGUMENT, "n must be at most 2^19");
-    if (m == 0 || m > 64u) return fail(RT_ERR_INVALID_ARGUMENT, "m must be within 1 .. 64");
-    if (min_spp < 2u || (min_spp & 1u) || (max_spp & 1u) || min_spp > max_spp || max_spp > rt::kAdaptiveMaxSpp)
-        return fail(RT_ERR_INVALID_ARGUMENT, "min_spp and max_spp must be even with 2 <= min_spp <= max_spp <= 2^19");
-    *next = rt::sample_map_feedback_count(E, S, n, m, thr_q16, min_spp, max_spp);
-    return RT_OK;
-}
-
-int rt_debug_hand_out(uint32_t n_units, uint64_t reserve, uint64_t grid_waves, uint32_t* n_block_units,
-                      uint32_t* first_blocks) {
-    if (!n_block_units || !first_blocks) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
-    const rt::HandOut h = rt::hand_out(n_units, reserve, grid_waves);
-    *n_block_units = h.n_block_units;
-    *first_blocks = h.first_blocks;
-    return RT_OK;
-}
-
-int rt_debug_sample_map_limit_blocks(rt_sample_map* map, uint64_t limit) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    map->limit_blocks = limit;
-    return RT_OK;
-}
-
-int rt_sample_map_get_info(const rt_sample_map* map, rt_sample_map_info* out) {
-    if (!map || !out) return fail(RT_ERR_INVALID_ARGUMENT, "map or out is NULL");
-    *out = map->info;
-    if (map->set && map->device_planned) {   // (levels and min_count stay 0: the planner does not count them)
-        rt::DeviceGuard g(map->ctx->device);
-        rt::sample_map::DeviceSummary s;
-        if (int rc = device_summary(map, &s)) return rc;
-        out->max_count = s.max_count;
-        out->samples = s.samples;
-        out->tile_launches = s.live_tiles;
-    }
-    return RT_OK;
-}
-
-int rt_sample_map_set_schedule(rt_sample_map* map, uint32_t schedule, uint32_t unit_samples) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    if (schedule != RT_SAMPLE_MAP_LEVELS && schedule != RT_SAMPLE_MAP_ONE_LAUNCH)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_schedule: unknown schedule " + std::to_string(schedule));
-    if (schedule == RT_SAMPLE_MAP_LEVELS && unit_samples != 0)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_sample_map_set_schedule: unit_samples must be 0 with RT_SAMPLE_MAP_LEVELS");
-    if (unit_samples > rt::sample_map::kMaxUnit)
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "rt_sample_map_set_schedule: unit_samples = " + std::to_string(unit_samples) + " is above 2^19");
-    map->next_schedule = schedule;
-    map->next_unit = unit_samples;
-    return RT_OK;
-}
-
-int rt_sample_map_get_schedule(const rt_sample_map* map, uint32_t* schedule, uint32_t* unit_samples_used,
-                               uint64_t* n_blocks) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    if (schedule) *schedule = map->schedule;
-    if (unit_samples_used) *unit_samples_used = map->unit_samples;
-    if (n_blocks) *n_blocks = map->n_blocks;
-    if (map->set && map->device_planned && (unit_samples_used || n_blocks)) {
-        rt::DeviceGuard g(map->ctx->device);
-        rt::sample_map::DeviceSummary s;
-        if (int rc = device_summary(map, &s)) return rc;
-        if (unit_samples_used) *unit_samples_used = s.unit_used;
-        if (n_blocks) *n_blocks = s.n_blocks;
-    }
-    return RT_OK;
-}
-
-int rt_sample_map_block_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t unit_samples,
-                             uint32_t* blocks_out, uint64_t capacity, uint64_t* n_blocks, uint32_t* unit_samples_used) {
-    std::string err;
-    if (int rc = rt::sample_map::block_plan_arrays(tile_counts, n_tiles, quantum, unit_samples, blocks_out, capacity,
-                                                   n_blocks, unit_samples_used, &err))
-        return fail(rc, err);
-    return RT_OK;
-}
-
-int rt_debug_sample_map_blocks(const rt_sample_map* map, uint32_t* out, uint64_t capacity, uint64_t* n) {
-    if (!map || !n) return fail(RT_ERR_INVALID_ARGUMENT, "map or n is NULL");
-    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: the map was never set");
-    rt::DeviceGuard g(map->ctx->device);
-    uint64_t n_blocks = map->n_blocks;
-    if (map->device_planned) {   // the count is the planner's
-        rt::sample_map::DeviceSummary s;
-        if (int rc = device_summary(map, &s)) return rc;
-        n_blocks = std::min<uint64_t>(s.n_blocks, map->cap_blocks);
-    }
-    if (out && capacity < n_blocks)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_blocks: capacity is below the table's " +
-                                                 std::to_string(n_blocks) + " blocks");
-    if (out && n_blocks) {
-        if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-        RT_HIP(hipMemcpy(out, map->blocks, n_blocks * sizeof(rt::BlockEntry), hipMemcpyDeviceToHost));
-    }
-    *n = n_blocks;
-    return RT_OK;
-}
-
-int rt_sample_map_plan(const uint32_t* tile_counts, uint32_t n_tiles, uint32_t quantum, uint32_t* order,
-                       uint32_t* levels, uint32_t* level_tiles, uint32_t* n_levels, uint32_t* quantised) {
-    std::string err;
-    if (int rc = rt::sample_map::plan_arrays(tile_counts, n_tiles, quantum, order, levels, level_tiles, n_levels,
-                                             quantised, &err))
-        return fail(rc, err);
-    return RT_OK;
-}
-
-int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, uint32_t band_height, uint32_t quantum,
-                             rt_sample_map_info* out) {
-    if (band_width == 0 || band_height == 0 || band_width > 65535u || band_height > 65535u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "band width and height must be within 1 .. 65535");
-    const uint32_t n_tiles = ((band_width + 7u) / 8u) * ((band_height + 7u) / 8u);
-    rt::sample_map::Plan plan;
-    std::string err;
-    if (int rc = rt::sample_map::make_plan(tile_counts, n_tiles, quantum, plan, &err)) return fail(rc, err);
-    if (int rc = rt::sample_map::totals(plan, band_width, band_height, out, &err)) return fail(rc, err);
-    return RT_OK;
-}
-
-int rt_debug_sample_map(const rt_sample_map* map, uint32_t* order, uint32_t* levels, uint32_t* level_tiles,
-                        uint32_t* quantised) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map: the map was never set");
-    rt::DeviceGuard g(map->ctx->device);
-    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-    const size_t n = map->n_tiles;
-    if (order) RT_HIP(hipMemcpy(order, map->table, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (quantised) RT_HIP(hipMemcpy(quantised, map->table + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    // (a one-launch plan may hold more levels than the arrays: the lowest RT_SAMPLE_MAP_MAX_LEVELS)
-    const size_t j = std::min<size_t>(map->plan.levels.size(), RT_SAMPLE_MAP_MAX_LEVELS);
-    if (levels) std::copy_n(map->plan.levels.begin(), j, levels);
-    if (level_tiles) std::copy_n(map->plan.level_tiles.begin(), j, level_tiles);
-    return RT_OK;
-}
-
-// The whole frame is queued: one trace launch per level on the nested prefixes of the map's order
-// (a one-launch plan: one launch of its block table), then the resolve with the map as per-tile
-// divisors. No host wait, no event synchronisation and no
-// blocking copy below (the buffers' first allocation and growth in adaptive_reserve aside).
-int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
-                                uint32_t band_height, float* accum, uint8_t* out, uint32_t* sample_count,
-                                const rt_options* opt, const rt_sample_map* map, void* stream) {
-    static const char* const who = "rt_render_sample_map_device";
-    rt_options o{};
-    bool empty = false;
-    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, &empty)) return rc;
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": map is NULL");
-    if (map->ctx != ctx) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map belongs to another context");
-    if (band_width != map->band_w || band_height != map->band_h)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": band size " + std::to_string(band_width) + " x " +
-                                                 std::to_string(band_height) + " is not the map's " +
-                                                 std::to_string(map->band_w) + " x " + std::to_string(map->band_h));
-    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map was never set");
-    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
-    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
-    const uint32_t cap = rci->samplesPerRenderCall;
-    if (map->device_planned && cap < map->count_cap)   // the host knows no more of such a map
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
-                                                 " is below the map's count_cap " + std::to_string(map->count_cap));
-    if (!map->device_planned && cap < map->info.max_count)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
-                                                 " is below the map's max_count " + std::to_string(map->info.max_count));
-    if (uint64_t(o.sample_base) + cap > 0xffffffffull)
-        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + samplesPerRenderCall overflows 32 bits");
-    rt_context::Adaptive& a = ctx->adaptive;
-    if (a.frame.open)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is open on this context");
-    rt::DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;
-    TraceSetup S;
-    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
-    const uint64_t texels = uint64_t(band_width) * band_height;
-    if (int rc = adaptive_reserve(ctx, texels, S.n_tiles, st)) return rc;
-    rt::TraceParams& P = S.P;
-    // the adaptive planes, half A alone (B stays zero; the resolve leaves both zero), and for the walk
-    // kernels' unconditional tile-cost record a scratch table behind everything an adaptive frame
-    // uses of `tiles`: the last adaptive frame's count table stays in place
-    P.fixed = a.planes;
-    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * a.cap_tiles : nullptr;
-    P.tile_order = map->table;
-    P.accumulate = 0u;
-    P.head_tiles = 0u;
-    // (after a failure between the first launch and the resolve the planes hold partial sums:
-    // abort_on_planes)
-    if (map->device_planned) {
-        // The table's size is device data: the launch takes it from the map's size record, filled on
-        // the stream from the planner's block count (launch_units), and runs on the full persistent
-        // grid, whatever the table holds (an empty one retires every wave at its first refill).
-        P.block_tab = map->blocks;
-        P.tab_size = map->tab_size;
-        P.tile_order = nullptr;
-        P.chunks = P.head_chunks = 1u;
-        P.n_units = 0u;
-        S.tab_blocks = &map->summary->n_blocks;
-        S.plan.lpt = 1u;
-        S.plan.chunks = S.plan.head_chunks = 1u;
-        S.plan.head_tiles = 0u;
-        S.plan.n_units = 0u;
-        rt::launch::hand_out_units(S.in, S.plan, true);
-        S.plan.grid = uint32_t(std::max<uint64_t>(1u, uint64_t(S.in.cu_count) * S.plan.blocks_per_cu));
-        if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
-    } else if (map->schedule == RT_SAMPLE_MAP_ONE_LAUNCH) {
-        if (map->n_blocks) {   // (an all-zero map: the resolve alone)
-            P.block_tab = map->blocks;
-            P.tile_order = nullptr;
-            P.chunks = P.head_chunks = 1u;
-            P.n_units = uint32_t(map->n_blocks * 64u);   // < 2^31 (rt_sample_map.h kMaxBlocks)
-            S.plan.lpt = 1u;
-            S.plan.chunks = S.plan.head_chunks = 1u;
-            S.plan.head_tiles = 0u;
-            S.plan.n_units = P.n_units;
-            rt::launch::hand_out_units(S.in, S.plan, true);
-            if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
-        }
-    }
-    uint32_t prev = 0;
-    for (size_t j = 0; map->schedule == RT_SAMPLE_MAP_LEVELS && j < map->plan.levels.size(); j++) {   // samples [L_{j-1}, L_j) on the first c_j tiles
-        const uint32_t level = map->plan.levels[j];
-        if (int rc = launch_tile_prefix(ctx, S, level - prev, o.sample_base + prev, map->plan.level_tiles[j], true, st))
-            return abort_on_planes(ctx, st, rc);
-        prev = level;
-    }
-    if (hipError_t e = rt::launch_adaptive_resolve(a.planes, a.planes + 3u * texels, texels, band_width, P.tiles_x,
-                                                   map->table + map->n_tiles, accum, out, sample_count, st);
-        e != hipSuccess)
-        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
-    RT_HIP(hipEventRecord(map->ev_read, st));   // the next set call waits for this frame
-    map->read_pending = true;
-    return render_issued(ctx, st);
-}
-
-// A feedback frame: the map's A half into planes A and its B half into planes B
-// (two table launches sized on the device), the update (the next counts from the two halves'
-// difference), the resolve (A + B by the map's counts; zeroes both) and the planner in halves mode
-// on the next counts. Everything is queued; the context orders it behind whatever it queued before,
-// so the one table of the map is rebuilt only after the frames that read it.
-int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
-                                         uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
-                                         uint32_t* sample_count, const rt_options* opt, rt_sample_map* map,
-                                         const rt_sample_map_feedback* fb, uint64_t* d_tile_error, void* stream) {
-    static const char* const who = "rt_render_sample_map_feedback_device";
-    rt_options o{};
-    bool empty = false;
-    if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, &empty)) return rc;
-    if (!map || !fb) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": map or feedback is NULL");
-    if (map->ctx != ctx) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map belongs to another context");
-    if (band_width != map->band_w || band_height != map->band_h)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": band size " + std::to_string(band_width) + " x " +
-                                                 std::to_string(band_height) + " is not the map's " +
-                                                 std::to_string(map->band_w) + " x " + std::to_string(map->band_h));
-    if (!map->set) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the map was never set");
-    if (o.rng_mode != RT_RNG_SAMPLE_HASH)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + " needs rng_mode RT_RNG_SAMPLE_HASH");
-    if (o.accumulate) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": accumulate must be 0");
-    const uint32_t cap = rci->samplesPerRenderCall;
-    if (cap & 1u) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) must be even");
-    if (!(std::isfinite(fb->threshold) && fb->threshold >= 0.0f && fb->threshold <= 16.0f))
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback threshold must be finite and within [0, 16]");
-    if (fb->min_spp < 2u || (fb->min_spp & 1u) || (fb->max_spp & 1u) || fb->min_spp > fb->max_spp ||
-        fb->max_spp > rt::kAdaptiveMaxSpp)
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    std::string(who) + ": feedback min_spp and max_spp must be even with 2 <= min_spp <= max_spp <= 2^19");
-    if (cap < fb->max_spp)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
-                                                 " is below the feedback max_spp " + std::to_string(fb->max_spp));
-    if (fb->unit_samples > rt::sample_map::kMaxUnit)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback unit_samples is above 2^19");
-    if (fb->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": feedback reserved must be 0");
-    const uint32_t held = map->device_planned ? map->count_cap : map->info.max_count;
-    if (cap < held)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samplesPerRenderCall (the cap) " + std::to_string(cap) +
-                                                 " is below the map's " + (map->device_planned ? "count_cap " : "max_count ") +
-                                                 std::to_string(held));
-    if (uint64_t(o.sample_base) + cap > 0xffffffffull)
-        return fail(RT_ERR_INVALID_ARGUMENT, "sample_base + samplesPerRenderCall overflows 32 bits");
-    if (map->n_tiles > rt::sample_map::kDeviceMaxBlocks)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": the band has more than 2^22 tiles");
-    rt_context::Adaptive& a = ctx->adaptive;
-    if (a.frame.open)
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": an adaptive frame is open on this context");
-    rt::DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = order_on(ctx, st)) return rc;
-    const size_t n = map->n_tiles;
-    if (!(map->device_planned && map->halves && map->count_cap == cap)) {
-        // the first feedback frame on this map (or at this cap): its current counts, in halves
-        if (int rc = queue_device_plan(map, map->table + n, fb->unit_samples, cap, true, st, who)) return rc;
-    }
-    TraceSetup S;
-    if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, S)) return rc;
-    const uint64_t texels = uint64_t(band_width) * band_height;
-    if (int rc = adaptive_reserve(ctx, texels, S.n_tiles, st)) return rc;
-    rt::TraceParams& P = S.P;
-    P.tile_cost = S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * a.cap_tiles : nullptr;
-    P.tile_order = nullptr;
-    P.accumulate = 0u;
-    P.head_tiles = 0u;
-    P.tab_size = map->tab_size;
-    P.chunks = P.head_chunks = 1u;
-    P.n_units = 0u;
-    S.tab_blocks = &map->summary->half_blocks;
-    S.plan.lpt = 1u;
-    S.plan.chunks = S.plan.head_chunks = 1u;
-    S.plan.head_tiles = 0u;
-    S.plan.n_units = 0u;
-    rt::launch::hand_out_units(S.in, S.plan, true);
-    S.plan.grid = uint32_t(std::max<uint64_t>(1u, uint64_t(S.in.cu_count) * S.plan.blocks_per_cu));
-    unsigned long long* half[2] = {a.planes, a.planes + 3u * texels};
-    for (int h = 0; h < 2; h++) {   // the B half's entries once more from entry 2 x half_capacity
-        P.fixed = half[h];
-        P.block_tab = map->blocks + (h ? 2u * map->half_capacity : 0u);
-        if (int rc = launch_units(ctx, S, st)) return abort_on_planes(ctx, st, rc);
-    }
-    rt::FeedbackParams F{};
-    F.a = half[0];
-    F.b = half[1];
-    F.texels = texels;
-    F.band_w = band_width;
-    F.band_h = band_height;
-    F.tiles_x = P.tiles_x;
-    F.n_tiles = map->n_tiles;
-    F.tile_n = map->table + n;
-    F.thr_q16 = rt::adaptive_thr_q16(fb->threshold);
-    F.min_spp = fb->min_spp;
-    F.max_spp = fb->max_spp;
-    F.next = map->next;
-    F.tile_error = reinterpret_cast<unsigned long long*>(d_tile_error);
-    F.moved = map->moved;
-    if (hipError_t e = rt::launch_feedback_update(F, st); e != hipSuccess)
-        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_feedback_update: ") + hipGetErrorString(e)));
-    if (hipError_t e = rt::launch_adaptive_resolve(half[0], half[1], texels, band_width, P.tiles_x, map->table + n, accum, out,
-                                                   sample_count, st);
-        e != hipSuccess)
-        return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
-    if (int rc = render_issued(ctx, st)) return rc;
-    // the next frame's table, from the counts the update chose (<= max_spp <= cap)
-    return queue_device_plan(map, nullptr, fb->unit_samples, cap, true, st, who);
-}
-
 int rt_debug_host_waits(rt_context* ctx, uint64_t* n) {
     if (!ctx || !n) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     *n = ctx->host_waits;
-    return RT_OK;
-}
-
-int rt_debug_sample_map_feedback(rt_sample_map* map, uint32_t* next, uint64_t* raised, uint64_t* lowered) {
-    if (!map) return fail(RT_ERR_INVALID_ARGUMENT, "map is NULL");
-    if (!map->next) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_sample_map_feedback: the map was never planned on the device");
-    rt::DeviceGuard g(map->ctx->device);
-    if (map->read_pending) RT_HIP(hipEventSynchronize(map->ev_read));
-    unsigned long long moved = 0;
-    RT_HIP(hipMemcpy(&moved, map->moved, sizeof(moved), hipMemcpyDeviceToHost));
-    if (next) RT_HIP(hipMemcpy(next, map->next, size_t(map->n_tiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (raised) *raised = moved & 0xffffffffull;
-    if (lowered) *lowered = moved >> 32;
     return RT_OK;
 }
 

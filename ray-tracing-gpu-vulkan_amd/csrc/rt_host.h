@@ -1,5 +1,5 @@
-// rt_host.h — error plumbing and device selection shared by the host runtime files
-// (rt_api.cpp, rt_multi.cpp). Not part of the public C-ABI.
+// rt_host.h — error plumbing and device selection shared by the host runtime files, and the narrow
+// interface of rt_multi.cpp to a context (the context itself: rt_context.h). Not part of the public C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,8 +37,9 @@ void keep_row_weights(rt_context* ctx);
 
 // The pass loop of an adaptive frame (rt_render_adaptive_device) as resumable
 // steps on a context, so that one host thread interleaves the passes of several contexts
-// (rt_multi_render_adaptive); rt_render_adaptive_device itself is a loop over them. (Here and not
-// in rt_internal.h: that header is compiled into the trace kernels' object.)
+// (rt_multi_render_adaptive); rt_render_adaptive_device itself is a loop over them, beside their
+// definitions in rt_adaptive_frame.cpp. (Here and not in rt_internal.h: that header is compiled
+// into the trace kernels' object.)
 //   adaptive_check  the argument checks alone, no device work: rt_render_adaptive_device's rules,
 //                   `who` names the caller in messages. *empty: a band without texels.
 //   adaptive_check_values  the part of them that needs no context (options, adaptive, the cap).
@@ -79,6 +80,8 @@ int adaptive_store_tiles(int device, const float* src, uint32_t n_rows, uint32_t
 // Message of the calling thread's last failure (rt_last_error()).
 extern thread_local std::string g_last_error;
 int fail(int code, const std::string& msg);
+// A failed HIP call of `who`: RT_ERR_OUT_OF_MEMORY or RT_ERR_DEVICE, message "who: <HIP's error string>".
+int fail_hip(hipError_t e, const std::string& who);
 // RT_ERR_INVALID_ARGUMENT for a scene whose sphere `index` has a NaN / inf centre or radius
 // (the geometry contract; rt_grid.h first_nonfinite_geometry).
 int refuse_nonfinite(uint32_t index);
@@ -98,10 +101,8 @@ struct DeviceGuard {
 
 }  // namespace rt
 
-#define RT_HIP(call)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return ::rt::fail(e_ == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_DEVICE, \
-                              std::string(#call) + ": " + hipGetErrorString(e_));          \
+#define RT_HIP(call)                                            \
+    do {                                                        \
+        hipError_t e_ = (call);                                 \
+        if (e_ != hipSuccess) return ::rt::fail_hip(e_, #call); \
     } while (0)

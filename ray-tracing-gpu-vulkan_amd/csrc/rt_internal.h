@@ -1,5 +1,6 @@
 // rt_internal.h — device data layout and launch parameters shared by the HIP kernels
-// (rt_kernels.hip) and the host runtime (rt_api.cpp). Not part of the public C-ABI.
+// (rt_kernels.hip) and the host runtime (rt_api.cpp and the frame kinds beside it, through
+// rt_context.h). Not part of the public C-ABI.
 #pragma once
 
 #include <stdint.h>

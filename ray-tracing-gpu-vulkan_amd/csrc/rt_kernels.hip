@@ -20,6 +20,7 @@
 
 #include "rt_device_math.h"
 #include "rt_internal.h"
+#include "rt_launchers.h"
 
 using namespace rtd;
 
@@ -2286,7 +2287,7 @@ __global__ __launch_bounds__(256) void rt_debug_exact_kernel(uint64_t base, floa
 
 }  // namespace
 
-// ---- host-callable launchers (rt_api.cpp) ---------------------------------------------------
+// ---- host-callable launchers (rt_launchers.h) -----------------------------------------------
 namespace rt {
 
 // TAB: the table form of the hand-out (TraceParams::block_tab), HASH launches only: 1 a table whose

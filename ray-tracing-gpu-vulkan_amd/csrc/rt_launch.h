@@ -5,7 +5,8 @@
 // (rt_debug_launch_plan, tests/test_launch_plan.py) and the sanitizer build (tests/native/Makefile
 // `sanitize`) exercise exactly the code rt_render_device runs. What only the kernels' translation
 // unit knows (the occupancy of a kernel form, its one-layer grid form, its block size) reaches the
-// plan through `Device`: rt_api.cpp passes the real ones, tests pass tables.
+// plan through `Device`: rt_api.cpp's fill_trace, which every frame kind goes through, passes the
+// real ones (rt_launchers.h), tests pass tables.
 #pragma once
 
 #include <cstddef>

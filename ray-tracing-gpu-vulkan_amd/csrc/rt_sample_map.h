@@ -3,7 +3,8 @@
 // ascending), the distinct non-zero counts L_0 < ... < L_{J-1} and the prefix lengths c_j = #{t :
 // n[t] >= L_j}. Launch j of the frame renders samples [L_{j-1}, L_j) on the first c_j tiles of the
 // order. Plain C++ so that the CPU tests (rt_sample_map_plan) and the sanitizer build
-// (tests/native/sample_map_plan_main.cpp) exercise exactly the code the set calls of rt_api.cpp run.
+// (tests/native/sample_map_plan_main.cpp) exercise exactly the code the set calls of
+// rt_sample_map_frame.cpp run.
 // The one-launch schedule (RT_SAMPLE_MAP_ONE_LAUNCH) renders the same table from a block table
 // instead: make_block_plan below.
 #pragma once

@@ -12,6 +12,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rt_internal.h"
+#include "rt_launchers.h"
 #include "rt_sample_map_device.h"
 
 using rt::sample_map::DevicePlanParams;

@@ -216,18 +216,26 @@ def test_refusals(lib, renderer, torch, oracle):
     renderer.set_scene(sim.scene(oracle))
     acc, out, cnt = sentinels(torch, W, H)
 
-    def refused(field, fb=None, spp=MAX, **opt):
+    def refused(field, fb=None, spp=MAX, m=None, r=renderer, **opt):
         o = dict(rng_mode=HASH)
         o.update(opt)
         with pytest.raises(RtError) as e:
-            renderer.render_sample_map_feedback(rci_of(lib, oracle, spp, W, H), acc, out, smap,
-                                                fb if fb is not None else lib.make_feedback(THR, LO, HI), sample_count=cnt,
-                                                options=lib.make_options(**o))
+            r.render_sample_map_feedback(rci_of(lib, oracle, spp, W, H), acc, out, m if m is not None else smap,
+                                         fb if fb is not None else lib.make_feedback(THR, LO, HI), sample_count=cnt,
+                                         options=lib.make_options(**o))
         assert e.value.code == -1 and field in str(e.value), str(e.value)
 
-    with renderer.sample_map(W, H) as smap:
+    with renderer.sample_map(W, H) as smap, renderer.sample_map(8, 8) as small:
+        refused("never set")
         set_map(torch, smap, START)
+        set_map(torch, small, [16])
         held = smap.info
+        # the checks shared with rt_render_sample_map_device (tests/test_sample_map.py::test_refusals)
+        refused("band size", m=small)                     # an 8x8 map for 44x27 buffers
+        refused("sample_base", sample_base=0xffffffff)
+        with lib.Renderer(0) as other:
+            other.set_scene(sim.scene(oracle))
+            refused("another context", r=other)
         refused("rng_mode", rng_mode=abi.RT_RNG_PIXEL_STREAM)
         refused("accumulate", accumulate=True)
         refused("must be even", spp=65)
