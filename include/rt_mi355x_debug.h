@@ -136,6 +136,22 @@ int rt_debug_sample_map_info(const uint32_t* tile_counts, uint32_t band_width, u
  * (zeros without a grid). *bytes = the array's size; RT_ERR_INVALID_ARGUMENT when it exceeds
  * capacity. */
 int rt_debug_scene(rt_context* ctx, uint32_t what, void* out, uint64_t capacity, uint64_t* bytes);
+/* Diagnostic (tests): the closest hit of n given rays in ctx's scene, by the production walk of the
+ * form `options` selects (accel, reserved[1] the form, reserved[0] bit 1 force_regate, as
+ * rt_render_device reads them; its other fields are ignored, NULL: zeros). rays6: n host rays {ox,
+ * oy, oz, vx, vy, vz}; the direction traced is the kernels' normalize(v), as for every segment of a
+ * frame, and every value must be finite and each v have a nonzero component (RT_ERR_INVALID_ARGUMENT
+ * otherwise, as for n above 2^24). The launch goes through the launch plan of a frame whose camera
+ * lies at the batch's largest |o| (form choice, cull slacks, the far-camera re-pad, the grid's
+ * refusal beyond its pad radius) and runs the form's trace kernel with a ray per unit, and
+ * rt_debug_launch_info reports it like any other launch. out_id[i]: the winning sphere of ray i,
+ * 0xffffffff for none; out_t[i]: its t (unspecified on a miss). Synchronous. n = 0: RT_OK, nothing
+ * written; RT_ERR_NO_SCENE before rt_set_scene. Leaves the images and the hand-out order of the
+ * frames around it alone. A batch with an origin beyond the radius the tree's node boxes are padded
+ * for re-pads them for it, as a frame with a far camera does, and ctx keeps the wider boxes (more
+ * conservative culling, the same answers) until its next rt_set_scene. */
+int rt_debug_closest_hits(rt_context* ctx, const float* rays6, uint32_t n, const rt_options* options,
+                          uint32_t* out_id, float* out_t);
 
 /*
  * The multi-device frame plan rt_multi_render (band_starts NULL: its first frame's row-exact strips,

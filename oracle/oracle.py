@@ -48,6 +48,10 @@ def lib() -> ctypes.CDLL:
         l.orc_generate_scene.argtypes = [ctypes.c_float, _U, _P, _U, ctypes.POINTER(_U)]
         l.orc_render.restype = _I
         l.orc_render.argtypes = [_P, _U, _P, _P, _U, _U, _P, _P, _P, _P, _I]
+        l.orc_closest_hits.restype = _I
+        l.orc_closest_hits.argtypes = [_P, _U, _P, _U, _I, _P, _P, _I]
+        l.orc_report_t.restype = _I
+        l.orc_report_t.argtypes = [_P, _U, _P, _U, _P, _P]
         l.orc_resolve.restype = _I
         l.orc_resolve.argtypes = [_P, ctypes.c_uint64, _U, _P]
         _lib = l
@@ -139,6 +143,34 @@ def render(spheres, rci, band_w: int, band_h: int, rows=None, opts=None, accum=N
                          st.ctypes.data, threads if threads else (os.cpu_count() or 1))
     assert r == 0
     return acc, out, tuple(int(v) for v in st)
+
+
+def closest_hits(spheres, rays, gated: bool = True, threads: int = 0):
+    """The contract's closest hit of each ray of `rays` [n, 6] = (o, v), traced along normalize(v).
+    Returns (ids uint32 [n], 0xffffffff for none; t float32 [n]). gated=False leaves the AABB test
+    out: the winner the quadratic alone would pick."""
+    sp = _as_u8(spheres)
+    n = sp.size // 80
+    r = np.ascontiguousarray(rays, np.float32)
+    assert r.ndim == 2 and r.shape[1] == 6
+    ids = np.zeros(r.shape[0], np.uint32)
+    t = np.zeros(r.shape[0], np.float32)
+    rc = lib().orc_closest_hits(sp.ctypes.data if n else None, n, r.ctypes.data, r.shape[0], int(bool(gated)),
+                                ids.ctypes.data, t.ctypes.data, threads if threads else (os.cpu_count() or 1))
+    assert rc == 0
+    return ids, t
+
+
+def report_t(spheres, rays, ids) -> np.ndarray:
+    """The t the quadratic reports for sphere ids[i] on ray i, before the [tmin, tmax] and AABB tests
+    (NaN: negative discriminant)."""
+    sp = _as_u8(spheres)
+    r = np.ascontiguousarray(rays, np.float32)
+    k = np.ascontiguousarray(ids, np.uint32)
+    assert r.ndim == 2 and r.shape[1] == 6 and k.shape == (r.shape[0],)
+    t = np.zeros(r.shape[0], np.float32)
+    assert lib().orc_report_t(sp.ctypes.data, sp.size // 80, r.ctypes.data, r.shape[0], k.ctypes.data, t.ctypes.data) == 0
+    return t
 
 
 def resolve(accum: np.ndarray, spp: int) -> np.ndarray:

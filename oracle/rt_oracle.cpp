@@ -269,7 +269,31 @@ inline bool aabb_hit(const rt_vec4& g, V3 o, V3 inv) {
 // overlaps its AABB and the quadratic reports t (t1 if t1 >= tmin, else t2) inside
 // [tmin, tmax]; the closest candidate wins, the lowest index on ties.
 // A report at exactly tMax is accepted (reportIntersectionEXT), hence '<' against succ(T_MAX).
+// shader.rint:22-60 for one sphere: the t the intersection shader would report before the range
+// test, t1 when t1 >= tmin, else t2; false when the discriminant is negative.
 template <int L>
+inline bool report_t(const rt_vec4& g, V3 o, V3 d, float a, float ia, float* t_out) {
+    V3 oc = sub(o, v3(g.x, g.y, g.z));
+    float b = dot<L>(oc, d);
+    float rr = g.w * g.w;
+    float c = dot<L>(oc, oc) - rr;
+    float D;
+    if (L == LIT_CONTRACT) {
+        D = std::fma(b, b, -(a * c));
+    } else {   // shader.rint:50 as written
+        float bb = b * b, ac = a * c;
+        D = bb - ac;
+    }
+    if (!(D >= 0.0f)) return false;
+    float sq = std::sqrt(D);
+    float t1 = L == LIT_CONTRACT ? (-b - sq) * ia : (-b - sq) / a;   // shader.rint:55-56 as written: / a
+    float t2 = L == LIT_CONTRACT ? (-b + sq) * ia : (-b + sq) / a;
+    *t_out = (t1 >= T_MIN) ? t1 : t2;   // rint:32-39 (t1 > tMax implies t2 > tMax)
+    return true;
+}
+
+// GATE = false (orc_closest_hits' gated = 0 only): without the AABB test, the winner of the quadratic alone.
+template <int L, bool GATE = true>
 Hit closest_hit(const Sphere* sph, uint32_t n, V3 o, V3 d, uint64_t* tests) {
     float a = dot<L>(d, d);
     float ia = 1.0f / a;
@@ -278,23 +302,9 @@ Hit closest_hit(const Sphere* sph, uint32_t n, V3 o, V3 d, uint64_t* tests) {
     int bi = -1;
     for (uint32_t i = 0; i < n; i++) {
         const rt_vec4& g = sph[i].geometry;
-        V3 oc = sub(o, v3(g.x, g.y, g.z));
-        float b = dot<L>(oc, d);
-        float rr = g.w * g.w;
-        float c = dot<L>(oc, oc) - rr;
-        float D;
-        if (L == LIT_CONTRACT) {
-            D = std::fma(b, b, -(a * c));
-        } else {   // shader.rint:50 as written
-            float bb = b * b, ac = a * c;
-            D = bb - ac;
-        }
-        if (D >= 0.0f) {
-            float sq = std::sqrt(D);
-            float t1 = L == LIT_CONTRACT ? (-b - sq) * ia : (-b - sq) / a;   // shader.rint:55-56 as written: / a
-            float t2 = L == LIT_CONTRACT ? (-b + sq) * ia : (-b + sq) / a;
-            float t = (t1 >= T_MIN) ? t1 : t2;   // rint:32-39 (t1 > tMax implies t2 > tMax)
-            if (t >= T_MIN && t < best && aabb_hit(g, o, inv)) { best = t; bi = int(i); }
+        float t;
+        if (report_t<L>(g, o, d, a, ia, &t)) {
+            if (t >= T_MIN && t < best && (!GATE || aabb_hit(g, o, inv))) { best = t; bi = int(i); }
         }
     }
     *tests += n;
@@ -622,6 +632,57 @@ int orc_render(const Sphere* spheres, uint32_t n, const RenderCallInfo* rci, con
     if (stats3) {
         stats3[0] = stats3[1] = stats3[2] = 0;
         for (auto& c : cnts) { stats3[0] += c.segments; stats3[1] += c.samples; stats3[2] += c.sphere_tests; }
+    }
+    return 0;
+}
+
+// The closest hit of n_rays given rays {ox, oy, oz, vx, vy, vz}, each traced along normalize(v) as
+// every segment of a frame is (checker of rt_debug_closest_hits): out_id the winning sphere
+// (0xffffffff: none), out_t its t (on a miss the search's start, succ(T_MAX)). gated = 0 leaves the
+// AABB test out. `threads` CPU threads (0 = hardware concurrency) take runs of 256 rays.
+int orc_closest_hits(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t n_rays, int gated,
+                     uint32_t* out_id, float* out_t, int threads) {
+    if ((!spheres && n) || (n_rays && (!rays6 || !out_id || !out_t))) return -1;
+    unsigned nt = threads > 0 ? unsigned(threads) : std::max(1u, std::thread::hardware_concurrency());
+    const uint32_t n_runs = (n_rays + 255u) / 256u;
+    nt = std::max(1u, std::min(nt, n_runs));
+    std::atomic<uint32_t> next_run{0};
+    auto worker = [&]() {
+        uint64_t tests = 0;
+        for (;;) {
+            const uint32_t r = next_run.fetch_add(1);
+            if (r >= n_runs) break;
+            for (uint32_t i = r * 256u; i < std::min(n_rays, r * 256u + 256u); i++) {
+                const float* q = rays6 + 6u * size_t(i);
+                const V3 o = v3(q[0], q[1], q[2]);
+                const V3 d = normalize<LIT_CONTRACT>(v3(q[3], q[4], q[5]));
+                const Hit h = gated ? closest_hit<LIT_CONTRACT, true>(spheres, n, o, d, &tests)
+                                    : closest_hit<LIT_CONTRACT, false>(spheres, n, o, d, &tests);
+                out_id[i] = uint32_t(h.idx);   // -1: 0xffffffff
+                out_t[i] = h.t;
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned i = 1; i < nt; i++) pool.emplace_back(worker);
+    worker();
+    for (auto& th : pool) th.join();
+    return 0;
+}
+
+// The t the quadratic reports for sphere ids[i] on ray i before any range or AABB test (NaN: negative
+// discriminant): what tests use to find rays whose t is exactly tmax or its successor.
+int orc_report_t(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t n_rays, const uint32_t* ids,
+                 float* out_t) {
+    if (!spheres || !rays6 || !ids || !out_t) return -1;
+    for (uint32_t i = 0; i < n_rays; i++) {
+        if (ids[i] >= n) return -1;
+        const float* q = rays6 + 6u * size_t(i);
+        const V3 d = normalize<LIT_CONTRACT>(v3(q[3], q[4], q[5]));
+        const float a = dot<LIT_CONTRACT>(d, d);
+        float t;
+        const bool real = report_t<LIT_CONTRACT>(spheres[ids[i]].geometry, v3(q[0], q[1], q[2]), d, a, 1.0f / a, &t);
+        out_t[i] = real ? t : std::numeric_limits<float>::quiet_NaN();
     }
     return 0;
 }

@@ -969,15 +969,24 @@ int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t
 // occupancy of the kernel form, on the caller's device and stream (after order_on).
 int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
                uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, TraceSetup& S) {
+    const float cam_r = std::sqrt(rci->camera_pos.x * rci->camera_pos.x + rci->camera_pos.y * rci->camera_pos.y +
+                                  rci->camera_pos.z * rci->camera_pos.z);
+    return fill_trace_at(ctx, rci, rows, band_width, band_height, o, accum, out, st, cam_r, -1, S);
+}
+
+// fill_trace for origins at most cam_r from the world origin, whatever rci's camera says (the
+// closest-hit probe's batch, rt_probe.cpp); pinhole_lf >= 0 sets TraceParams::pinhole_lf.
+int fill_trace_at(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                  uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, float cam_r,
+                  int pinhole_lf, TraceSetup& S) {
     const uint32_t spp = rci->samplesPerRenderCall;
     const uint64_t tiles_x = (band_width + 7u) / 8u, tiles_y = (band_height + 7u) / 8u;
     const uint64_t n_tiles = tiles_x * tiles_y;
     const rt::DeviceScene& d = ctx->scene;
-    const float cam_r = std::sqrt(rci->camera_pos.x * rci->camera_pos.x + rci->camera_pos.y * rci->camera_pos.y +
-                                  rci->camera_pos.z * rci->camera_pos.z);
     rt::TraceParams P;
     std::memset(&P, 0, sizeof(P));
     fill_camera(*rci, P);
+    if (pinhole_lf >= 0) P.pinhole_lf = uint32_t(pinhole_lf);
     // the form half of the launch plan (rt_launch.h): kernel form, LDS bytes, cull slack, occupancy
     rt::launch::Inputs& in = S.in;
     scene_inputs(ctx, in);

@@ -222,6 +222,9 @@ int check_render_args(const rt_context* ctx, const RenderCallInfo* rci, uint32_t
                       bool* empty);
 int fill_trace(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
                uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, TraceSetup& S);
+int fill_trace_at(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                  uint32_t band_height, const rt_options& o, float* accum, uint8_t* out, hipStream_t st, float cam_r,
+                  int pinhole_lf, TraceSetup& S);
 int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st);
 int launch_tile_prefix(rt_context* ctx, TraceSetup& S, uint32_t spp, uint32_t sample_base, uint64_t c, bool ordered,
                        hipStream_t st);

@@ -144,7 +144,9 @@ enum : uint32_t { ACCEL_BRUTE = 1, ACCEL_LBVH_GLOBAL = 2, ACCEL_LBVH_LDS = 3, AC
 //   HASH:   RT_RNG_SAMPLE_HASH: sample s restarts the LCG at sample_seed(pixel_seed, s); per-sample
 //           colours summed as 8.24 fixed point with integer atomics, so a pixel's samples may be
 //           split into chunks on any lanes / GPUs in any order and the sum is the same bits.
-enum : int { MODE_STREAM = 0, MODE_HASH = 1 };
+//   PROBE:  diagnostic (rt_debug_closest_hits): a unit is one given ray (TraceParams::probe_rays), whose
+//           closest hit is stored instead of shaded; no random stream and no image.
+enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2 };
 
 // Top treelet of a tree too big for LDS (ACCEL_LBVH_TOP): the nodes of depth <= kTreeletDepth in
 // the tree's depth-first order, 2 float4 each, AB layout: A = (lo.x, lo.y, hi.x, hi.y),
@@ -266,6 +268,10 @@ struct TraceParams {
                                    // come from this device record, read once at kernel entry (a table
                                    // planned on the device, whose size the host does not know), and
                                    // the three fields above are unused
+    // PROBE launches (rt_probe.cpp; launch_trace picks the kernels' MODE_PROBE instantiation when
+    // probe_rays is set): texel i = ly * band_w + lx of the band is ray i
+    const float* probe_rays;       // band_w * band_h rays {ox, oy, oz, vx, vy, vz}, v before normalisation
+    uint32_t* probe_out;           // per ray {winning sphere or 0xffffffff, bits of its t}
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,

@@ -744,6 +744,7 @@ __device__ __forceinline__ void store_pixel(const rt::TraceParams& P, const Path
 // partial fixed-point sum.
 template <int MODE, bool LSUM>
 __device__ __forceinline__ void finish_unit(const rt::TraceParams& P, Path& ps) {
+    if constexpr (MODE == rt::MODE_PROBE) return;   // the ray's record is already stored (shade_rec)
     if (MODE == rt::MODE_HASH && LSUM) {   // the unit's whole sum from LDS, once
         unsigned long long* s = lane_sum_slot();
         const unsigned long long x = s[0] + ps.qx, y = s[RT_TRACE_BLOCK] + ps.qy, z = s[2 * RT_TRACE_BLOCK] + ps.qz;
@@ -822,7 +823,14 @@ __device__ __forceinline__ bool start_sample(const rt::TraceParams& P, const Cam
         return false;
     }
     V3 v;
-    camera_ray<MODE, FAST>(P, cam, ps, o, v);
+    if constexpr (MODE == rt::MODE_PROBE) {   // the unit's texel is a ray of the caller's batch
+        const float* q = P.probe_rays + 6u * (size_t(ps.px >> 16) * P.band_w + (ps.px & 0xffffu));
+        o = v3(q[0], q[1], q[2]);
+        v = v3(q[3], q[4], q[5]);
+        ps.depth = 0;
+    } else {
+        camera_ray<MODE, FAST>(P, cam, ps, o, v);
+    }
     d = normalize(v);
     return true;
 }
@@ -873,6 +881,12 @@ __device__ __forceinline__ HitRec load_hit_rec(uint32_t bi) {
 template <int MODE, bool LSUM, bool FAST = false>
 __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera& cam, const HitRec& hr, Path& ps,
                                           uint32_t bi, float best, V3& o, V3& d, bool& fresh) {
+    if constexpr (MODE == rt::MODE_PROBE) {   // the closest hit is the answer: no shading, the unit ends
+        const size_t i = size_t(ps.px >> 16) * P.band_w + (ps.px & 0xffffu);
+        P.probe_out[2 * i] = bi;
+        P.probe_out[2 * i + 1] = __float_as_uint(best);
+        return false;
+    }
     V3 att;
     bool scatter = false;
     V3 sd = v3(0.0f, 0.0f, 0.0f);
@@ -973,7 +987,9 @@ __device__ __forceinline__ bool shade(const rt::TraceParams& P, const Camera& ca
 // frame ends with the longest chain.
 template <int MODE>
 __device__ __forceinline__ void record_tile_cost(const rt::TraceParams& P, const Path& ps) {
-    // (P.tile_cost is set for every walk kernel, the only callers)
+    // (P.tile_cost is set for every walk kernel, the only callers; a probe launch has none and leaves
+    // the context's LPT record alone)
+    if constexpr (MODE == rt::MODE_PROBE) return;
     if (MODE == rt::MODE_HASH && (ps.px & 0x00010001u)) return;
     const uint32_t lx = ps.px & 0xffffu, ly = ps.px >> 16;
     uint32_t* c = &P.tile_cost[(ly >> 3) * P.tiles_x + (lx >> 3)];
@@ -1084,13 +1100,19 @@ enum : int { LAYOUT_GLOBAL = 0, LAYOUT_LDS1 = 1, LAYOUT_OCT = 2, LAYOUT_TOP = 3,
 // inf - inf = NaN for a plane on the far side of the origin and cull a box the ray runs inside, so
 // the node reciprocal is clamped to +-2^100: the slab then spans (-huge, +huge) exactly when the
 // origin lies inside the padded slab, which is what the gate's (plane - o) * inf gives.
+// The same holds for a reciprocal that is finite but beyond 2^100 (a direction component below
+// 2^-100, e.g. a denormal one): o * inv overflows to inf once |o| |inv| reaches 2^128, and the
+// slab becomes (-inf, NaN), a cull of a box the ray runs inside (found by the closest-hit probe:
+// tests/test_gpu_closest_hit.py test_denormal_direction_regression). Along such an axis the ray
+// moves less than tmax 2^-100, far less than the boxes' padding, so it is inside the padded slab for
+// its whole length or never: every |inv| > 2^100 is clamped, not the infinite one alone.
 // Node layout "AB" (LDS): A = (x0, y0, x1, y1), B = (z0, z1, miss link, hit link). OCT: the node
 // copy is specialised to the ray's direction octant, (x0, y0, z0) are the near planes and (x1, y1,
 // z1) the far ones, so no per-axis min/max is needed.
 struct RayBox { V3 inv, oi; };
 
 __device__ __forceinline__ float node_inv(float inv) {
-    return __builtin_isinf(inv) ? __builtin_copysignf(0x1p100f, inv) : inv;
+    return __builtin_fabsf(inv) > 0x1p100f ? __builtin_copysignf(0x1p100f, inv) : inv;
 }
 __device__ __forceinline__ RayBox ray_box(const V3 o, const V3 inv) {
     const V3 n = v3(node_inv(inv.x), node_inv(inv.y), node_inv(inv.z));
@@ -2294,49 +2316,52 @@ namespace rt {
 // size is in the kernel argument, 2 one whose size is a device record (TraceParams::tab_size). Two
 // instantiations, not a branch on P.tab_size: the host-table kernels keep their source (DESIGN.md
 // §3.1.2 measured the one-instantiation form 0.4-1 % slower on them).
-template <int MODE, int TAB>
-static const void* pick_mode(uint32_t accel, bool count, bool flat) {
+// The one table from a launch's form to its kernel. COUNT is a template argument so that a mode
+// instantiates only the instrumented kernels it has (pick_mode).
+template <int MODE, int TAB, bool COUNT>
+static const void* pick_form(uint32_t accel, bool flat) {
 #define RT_FN(...) reinterpret_cast<const void*>(__VA_ARGS__)
-#define RT_GRID(C, IN_LDS, COOP, REC, CQ, FLAT) RT_FN(rt_trace_grid_kernel<C, MODE, IN_LDS, COOP, REC, CQ, FLAT, TAB>)
-    if (flat && !count) {   // the grid walks of one-layer grids (instrumented builds count the same cells)
-        switch (accel) {
-            case ACCEL_GRID: return RT_GRID(false, true, false, false, false, true);
-            case ACCEL_GRID_REC: return RT_GRID(false, true, false, true, false, true);
-            case ACCEL_GRID_GLOBAL: return RT_GRID(false, false, false, false, false, true);
-            default: break;
+#define RT_GRID(IN_LDS, COOP, REC, CQ, FLAT) RT_FN(rt_trace_grid_kernel<COUNT, MODE, IN_LDS, COOP, REC, CQ, FLAT, TAB>)
+    if constexpr (!COUNT) {   // the grid walks of one-layer grids (instrumented builds count the same cells
+                              // with the general form: they have no one-layer kernels)
+        if (flat) {
+            switch (accel) {
+                case ACCEL_GRID: return RT_GRID(true, false, false, false, true);
+                case ACCEL_GRID_REC: return RT_GRID(true, false, true, false, true);
+                case ACCEL_GRID_GLOBAL: return RT_GRID(false, false, false, false, true);
+                default: break;
+            }
         }
     }
     switch (accel) {
-        case ACCEL_BRUTE:
-            return count ? RT_FN(rt_trace_brute_kernel<true, MODE, TAB>) : RT_FN(rt_trace_brute_kernel<false, MODE, TAB>);
-        case ACCEL_LBVH_LDS:
-            return count ? RT_FN(rt_trace_lds_kernel<true, 1u, MODE, TAB>) : RT_FN(rt_trace_lds_kernel<false, 1u, MODE, TAB>);
-        case ACCEL_LBVH_OCT:
-            return count ? RT_FN(rt_trace_lds_kernel<true, 8u, MODE, TAB>) : RT_FN(rt_trace_lds_kernel<false, 8u, MODE, TAB>);
-        case ACCEL_LBVH_TOP:
-            return count ? RT_FN(rt_trace_top_kernel<true, MODE, TAB>) : RT_FN(rt_trace_top_kernel<false, MODE, TAB>);
-        case ACCEL_GRID:
-            return count ? RT_GRID(true, true, false, false, false, false) : RT_GRID(false, true, false, false, false, false);
-        case ACCEL_GRID_COOP:
-            return count ? RT_GRID(true, true, true, false, false, false) : RT_GRID(false, true, true, false, false, false);
-        case ACCEL_GRID_REC:
-            return count ? RT_GRID(true, true, false, true, false, false) : RT_GRID(false, true, false, true, false, false);
-        case ACCEL_GRID_CQ:
-            return count ? RT_GRID(true, true, false, false, true, false) : RT_GRID(false, true, false, false, true, false);
-        case ACCEL_GRID_REC_CQ:
-            return count ? RT_GRID(true, true, false, true, true, false) : RT_GRID(false, true, false, true, true, false);
-        case ACCEL_GRID_GLOBAL_COOP:
-            return count ? RT_GRID(true, false, true, false, false, false) : RT_GRID(false, false, true, false, false, false);
-        case ACCEL_GRID_GLOBAL:
-            return count ? RT_GRID(true, false, false, false, false, false) : RT_GRID(false, false, false, false, false, false);
-        default:
-            return count ? RT_FN(rt_trace_global_kernel<true, MODE, TAB>) : RT_FN(rt_trace_global_kernel<false, MODE, TAB>);
+        case ACCEL_BRUTE: return RT_FN(rt_trace_brute_kernel<COUNT, MODE, TAB>);
+        case ACCEL_LBVH_LDS: return RT_FN(rt_trace_lds_kernel<COUNT, 1u, MODE, TAB>);
+        case ACCEL_LBVH_OCT: return RT_FN(rt_trace_lds_kernel<COUNT, 8u, MODE, TAB>);
+        case ACCEL_LBVH_TOP: return RT_FN(rt_trace_top_kernel<COUNT, MODE, TAB>);
+        case ACCEL_GRID: return RT_GRID(true, false, false, false, false);
+        case ACCEL_GRID_COOP: return RT_GRID(true, true, false, false, false);
+        case ACCEL_GRID_REC: return RT_GRID(true, false, true, false, false);
+        case ACCEL_GRID_CQ: return RT_GRID(true, false, false, true, false);
+        case ACCEL_GRID_REC_CQ: return RT_GRID(true, false, true, true, false);
+        case ACCEL_GRID_GLOBAL_COOP: return RT_GRID(false, true, false, false, false);
+        case ACCEL_GRID_GLOBAL: return RT_GRID(false, false, false, false, false);
+        default: return RT_FN(rt_trace_global_kernel<COUNT, MODE, TAB>);
     }
 #undef RT_GRID
 #undef RT_FN
 }
 
+// PROBE launches (rt_debug_closest_hits) are never instrumented: that mode has no COUNT kernels.
+template <int MODE, int TAB>
+static const void* pick_mode(uint32_t accel, bool count, bool flat) {
+    if constexpr (MODE != MODE_PROBE) {
+        if (count) return pick_form<MODE, TAB, true>(accel, flat);
+    }
+    return pick_form<MODE, TAB, false>(accel, flat);
+}
+
 static const void* pick(uint32_t accel, bool count, int mode, bool flat, int tab = 0) {
+    if (mode == MODE_PROBE) return pick_mode<MODE_PROBE, 0>(accel, false, flat);
     if (mode != MODE_HASH) return pick_mode<MODE_STREAM, 0>(accel, count, flat);
     if (tab == 2) return pick_mode<MODE_HASH, 2>(accel, count, flat);
     return tab ? pick_mode<MODE_HASH, 1>(accel, count, flat) : pick_mode<MODE_HASH, 0>(accel, count, flat);
@@ -2353,7 +2378,9 @@ uint32_t block_size(uint32_t accel) { return accel == ACCEL_BRUTE ? kBruteBlock 
 hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mode, int grid, size_t lds_bytes,
                         hipStream_t st) {
     void* args[] = {const_cast<TraceParams*>(&P)};
-    // (the table form's occupancy is its uniform twin's: the same launch bounds and LDS)
+    // (the table form's occupancy is its uniform twin's: the same launch bounds and LDS; a probe
+    // launch is planned as the STREAM launch of its band)
+    if (P.probe_rays) mode = MODE_PROBE;
     return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count), P.block_tab ? (P.tab_size ? 2 : 1) : 0), dim3(grid),
                            dim3(block_size(accel)),
                            args, lds_bytes, st);

@@ -231,6 +231,23 @@ class Renderer:
         a = buf[: nbytes.value].view(dt)
         return a.reshape(-1, w) if w > 1 else a
 
+    def closest_hits(self, rays, options: Optional[Options] = None):
+        """Diagnostic (rt_debug_closest_hits): the closest hit of each of n host rays [n, 6] = (o, v)
+        by the production walk `options` selects (accel, reserved[1] the form, reserved[0] bit 1
+        force_regate, as render_device reads them), traced along the
+        kernels' normalize(v). Returns (ids uint32 [n], 0xffffffff for none; t float32 [n],
+        unspecified on a miss). Synchronous; launch_info() then describes the probe's launch."""
+        r = np.ascontiguousarray(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("rays must have shape [n, 6]")
+        n = r.shape[0]
+        ids = np.zeros(n, np.uint32)
+        t = np.zeros(n, np.float32)
+        check(self._lib.rt_debug_closest_hits(self._ctx, r.ctypes.data if n else None, n,
+                                              ctypes.byref(options) if options is not None else None,
+                                              ids.ctypes.data if n else None, t.ctypes.data if n else None))
+        return ids, t
+
     def render_device(self, rci: RenderCallInfo, accum, out, rows=None,
                       options: Optional[Options] = None, stream=None) -> None:
         """One band on this device, asynchronous on `stream` (torch current stream by default).

@@ -13,6 +13,7 @@
 //     device times and row weights, malformed inputs; the tile-row partition and plan of adaptive
 //     frames; every group of every plan through the pairing the logical transport executes
 //     (pair_group), and mutilated groups refused;
+//   * the closest-hit probe's batch staging (csrc/rt_probe_batch.cpp) and the oracle's closest-hit entries;
 //   * the single-device launch plan and the row weights (csrc/rt_launch.cpp): scenes, bands, sample
 //     counts, streams, forms and tuning values of tests/test_launch_plan.py plus the extremes (one
 //     CU, 1x1 and 65535x65535 bands, 0 samples, no spheres, tuning values up to 2^32), every plan
@@ -39,10 +40,15 @@
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_bvh.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_grid.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_launch.h"
+#include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_probe_batch.h"
 #include "../../ray-tracing-gpu-vulkan_amd/csrc/rt_plan.h"
 
 extern "C" {
 int orc_generate_scene(float t, uint32_t K, Sphere* out, uint32_t capacity, uint32_t* count);
+int orc_closest_hits(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t n_rays, int gated,
+                     uint32_t* out_id, float* out_t, int threads);
+int orc_report_t(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t n_rays, const uint32_t* ids,
+                 float* out_t);
 int orc_render(const Sphere* spheres, uint32_t n, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_w,
                uint32_t band_h, const rt_options* opt, float* accum, uint8_t* out, uint64_t* stats3, int threads);
 int orc_resolve(const float* acc, uint64_t n_texels, uint32_t spp, uint8_t* out);
@@ -606,6 +612,53 @@ void check_oracle() {
     }
 }
 
+// The host half of rt_debug_closest_hits (csrc/rt_probe_batch.cpp): batches that end inside a band
+// row, on one and one past it, the refusals, and the oracle's closest-hit entries on the staged band.
+void check_probe_batch() {
+    using rt::probe::kProbeBandW;
+    using rt::probe::stage_batch;
+    const std::vector<Sphere> s = scene(0.0f, 11);
+    for (uint32_t n : {1u, 63u, kProbeBandW - 1u, kProbeBandW, kProbeBandW + 1u, 3u * kProbeBandW + 7u}) {
+        std::vector<float> in(size_t(n) * 6u);   // exactly n rays: a read past them is a heap overflow
+        for (uint32_t i = 0; i < n; i++) {
+            const float q[6] = {0.01f * float(i), 1.0f, -3.0f + 0.001f * float(i), 0.0f, -0.1f, 1.0f};
+            std::memcpy(&in[6u * i], q, sizeof(q));
+        }
+        in[6u * (n / 2u) + 0] = -40.0f;   // the far origin
+        std::vector<float> rays;
+        uint32_t band_h = 0;
+        float cam_r = -1.0f;
+        CHECK(stage_batch(in.data(), n, rays, &band_h, &cam_r) == 0);
+        CHECK(band_h == (n + kProbeBandW - 1u) / kProbeBandW && rays.size() == size_t(band_h) * kProbeBandW * 6u);
+        CHECK(std::memcmp(rays.data(), in.data(), in.size() * sizeof(float)) == 0);
+        for (size_t i = n; i < size_t(band_h) * kProbeBandW; i++)
+            CHECK(std::memcmp(&rays[6u * i], in.data(), 6u * sizeof(float)) == 0);
+        const float* f = &in[6u * (n / 2u)];
+        CHECK(cam_r == std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]));
+        // the staged band through the oracle's entries (every texel is a valid ray)
+        const uint32_t texels = band_h * kProbeBandW;
+        std::vector<uint32_t> ids(texels), ungated(texels);
+        std::vector<float> t(texels), t2(texels), raw(texels);
+        CHECK(orc_closest_hits(s.data(), uint32_t(s.size()), rays.data(), texels, 1, ids.data(), t.data(), 3) == 0);
+        CHECK(orc_closest_hits(s.data(), uint32_t(s.size()), rays.data(), texels, 0, ungated.data(), t2.data(), 1) == 0);
+        std::vector<uint32_t> which(texels, 0u);
+        CHECK(orc_report_t(s.data(), uint32_t(s.size()), rays.data(), texels, which.data(), raw.data()) == 0);
+        for (uint32_t i = 0; i < texels; i++) CHECK(ids[i] == 0xffffffffu || ids[i] < s.size());
+        for (int k = 0; k < 6; k++) {   // refusals: the first bad ray's index + 1, nothing staged past it
+            std::vector<float> bad = in;
+            bad[6u * (n - 1u) + k] = k % 2 ? INFINITY : NAN;
+            CHECK(stage_batch(bad.data(), n, rays, &band_h, &cam_r) == n);
+        }
+        std::vector<float> bad = in;
+        bad[3] = 0.0f; bad[4] = -0.0f; bad[5] = 0.0f;
+        CHECK(stage_batch(bad.data(), n, rays, &band_h, &cam_r) == 1u);
+        bad = in;
+        bad[1] = 3e38f;   // finite, |o|^2 overflows
+        CHECK(stage_batch(bad.data(), n, rays, &band_h, &cam_r) == 1u);
+    }
+    CHECK(orc_closest_hits(nullptr, 0, nullptr, 0, 1, nullptr, nullptr, 2) == 0);   // nothing to do
+}
+
 }  // namespace
 
 int main() {
@@ -643,6 +696,7 @@ int main() {
     check_plans();
     check_launch_plans();
     check_oracle();
+    check_probe_batch();
     std::printf("sanitize harness: %d checks passed (ASan + UBSan)\n", g_checks);
     return 0;
 }

@@ -108,6 +108,9 @@ def test_invalid_arguments(rtvk):
     assert cnt.value == 488
     assert b"capacity" in lib.rt_last_error()
     assert lib.rt_render(None, 0, None, 0, None, None, None, None) == -1
+    # the closest-hit probe (rt_mi355x_debug.h): no context, before any device work
+    assert lib.rt_debug_closest_hits(None, None, 0, None, None, None) == -1
+    assert b"ctx" in lib.rt_last_error()
 
 
 def test_store_ppm(rtvk, tmp_path):

@@ -6,6 +6,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import closest_hit_cases as ch
+
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
 # SURVEY.md §4 pin 1: random.glsl restated in C and Python during the survey.
@@ -269,3 +271,88 @@ def test_literal_form_contract_unchanged(oracle):
     a0, p0, _ = oracle.render(sc, rci, 40, 24)
     a1, p1, _ = oracle.render(sc, rci, 40, 24, opts=oracle.options(lit=oracle.LIT_CONTRACT))
     assert np.array_equal(a0, a1) and np.array_equal(p0, p1)
+
+
+# ---- the closest-hit checker (orc_closest_hits) against float64 and against orc_render --------
+
+@pytest.fixture(scope="module")
+def generic_f64(oracle):
+    """Per scene: the generic family, the oracle's answers and float64's, computed once."""
+    memo = {}
+
+    def get(name):
+        if name not in memo:
+            sc = ch.make_scene(oracle, name)
+            rays = ch.generic(ch.geometry(sc), ch.N_RAYS_BIG if name == "big" else ch.N_RAYS)
+            memo[name] = (sc, rays, oracle.closest_hits(sc, rays), ch.closest_hits_f64(ch.geometry(sc), rays))
+        return memo[name]
+    return get
+
+
+@pytest.mark.parametrize("scene", ch.SCENES + ("big",))
+def test_closest_hits_agree_with_float64(oracle, generic_f64, scene):
+    """Two restatements of one contract can share a mistake: the oracle's closest hit (binary32,
+    the contract's operation order, gated) against the plain quadratic in float64 (closest t in
+    [tmin, tmax], lowest index on ties) on the generic family. On the rays float64 can decide
+    (closest_hit_cases.decided: the best two candidates apart, no discriminant near 0, no root near
+    tmin or tmax) the winner is the same and t agrees within T_TOL_U * 2^-24 * tscale; at most 5 %
+    of the family may be undecided."""
+    sc, rays, (ids, t), (fi, ft, gap, disc, edge, tscale) = generic_f64(scene)
+    dec = ch.decided(ft, gap, disc, edge)
+    hit = dec & (fi != ch.MISS)
+    ratio = np.abs(t[hit].astype(np.float64) - ft[hit]) / (2.0 ** -24 * tscale[hit])
+    wrong = np.flatnonzero(ids != fi)
+    print(f"{scene}: undecided {1 - dec.mean():.4f}, winners that differ {len(wrong)} (largest disc "
+          f"{disc[wrong].max() if len(wrong) else 0:.3g}, smallest gap / max(1, t) "
+          f"{(gap[wrong] / np.maximum(1, np.where(np.isfinite(ft[wrong]), ft[wrong], 1))).min() if len(wrong) else np.inf:.3g}, "
+          f"smallest edge {edge[wrong].min() if len(wrong) else np.inf:.3g}), worst |t - t64| / (u tscale) "
+          f"{ratio.max():.3g}")
+    assert 1 - dec.mean() <= ch.UNDECIDED_MAX
+    bad = np.flatnonzero(dec & (ids != fi))
+    assert bad.size == 0, [(int(i), int(ids[i]), int(fi[i]), float(t[i]), float(ft[i])) for i in bad[:4]]
+    assert ratio.max() <= ch.T_TOL_U
+    assert (fi != ch.MISS).mean() > 0.5 and (fi == ch.MISS).mean() > 0.05   # the family hits and misses
+
+
+@pytest.mark.parametrize("scene", ch.SCENES + ("big",))
+def test_tangent_family_has_rounding_corners(oracle, scene):
+    """The tangent family's condition on its own inputs: at least 32 rays whose ungated winner
+    (the quadratic alone) fails the AABB gate, so that the contract's winner is another sphere or
+    none. These are the rays on which a walk must notice that its winner is not the answer."""
+    sc = ch.make_scene(oracle, scene)
+    rays = ch.tangent(ch.geometry(sc), ch.N_RAYS_BIG if scene == "big" else ch.N_RAYS)
+    gi, _ = oracle.closest_hits(sc, rays)
+    ui, _ = oracle.closest_hits(sc, rays, gated=False)
+    corners = int(((ui != gi) & (ui != ch.MISS)).sum())
+    print(f"{scene}: {corners} corners of {len(rays)}")
+    assert corners >= 32
+    assert np.all((ui == gi) | (ui != ch.MISS))   # the gate only ever removes candidates
+
+
+def test_closest_hits_match_render_hit_pattern(oracle):
+    """orc_closest_hits against orc_render: a 1-spp, depth-1 frame ends at its camera ray's closest
+    hit (a miss returns the sky colour, a hit black or the absorbing material's colour), so its
+    hit-or-miss pattern is the probe's on the same camera rays (shader.rgen:56-58, 107-115 restated
+    with numpy in binary32)."""
+    W, H = 64, 36
+    sc = oracle.generate_scene()
+    rci = oracle.render_call_info(1, W, H)
+    f = rci.view(np.float32)
+    f[8:11] = [13.0, 1.0, 3.0]       # a low camera: the horizon crosses the frame
+    f[12:15] = [-13.0, 0.5, -3.0]
+    acc, _, _ = oracle.render(sc, rci, W, H, opts=oracle.options(max_depth=1))
+    vp = np.zeros(18, np.float32)
+    oracle.lib().orc_viewport(rci.ctypes.data, vp.ctypes.data)
+    look_from, hor, ver, ulc = vp[0:3], vp[3:6], vp[6:9], vp[9:12]
+    rays = np.zeros((H * W, 6), np.float32)
+    for y in range(H):
+        for x in range(W):
+            r0, r1 = oracle.random_floats(oracle.pixel_seed(x, y), 2)
+            ux = (np.float32(x) + np.float32(r0)) / np.float32(W)
+            uy = (np.float32(y) + np.float32(r1)) / np.float32(H)
+            to = (ulc + ux * hor) - uy * ver
+            rays[y * W + x] = np.concatenate([look_from, to - look_from])
+    ids, _ = oracle.closest_hits(sc, rays)
+    sky = np.all(acc[..., :3] == np.float32([0.7, 0.8, 1.0]), axis=-1).reshape(-1)
+    np.testing.assert_array_equal(sky, ids == ch.MISS)
+    assert 0.1 < sky.mean() < 0.9
