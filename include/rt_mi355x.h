@@ -449,6 +449,74 @@ int rt_gather_rows(rt_context* ctx, const float* src_accum, const uint32_t* rows
 int rt_resolve_rgba8(rt_context* ctx, const float* accum_rgba32f, uint64_t n_texels, uint32_t spp,
                      uint8_t* out_rgba8, void* stream);
 
+/*
+ * First-hit feature buffers: what a denoiser is guided by. For texel p of the
+ * band and every s in [opt->sample_base, opt->sample_base + feature_samples), the call traces
+ * exactly the camera ray rt_render_device traces for sample s under RT_RNG_SAMPLE_HASH (the same
+ * pixel seed, the same two jitter draws and lens draws; seed_mode, rows, rci->offset and
+ * rci->number are honoured alike) to its closest hit under the geometry contract ((t, lowest id),
+ * tmin / tmax, the AABB gate) and ends there. Per sample, by the expressions the shading uses
+ * (p = fma(t, d, o), outward = normalize(p - c), front = dot(d, outward) < 0, the checker):
+ *     hit:   albedo = colors[0], or colors[1] where a checkered sphere's checker is not positive;
+ *            n = front ? outward : -outward;  depth = t;  hit = 1
+ *     miss:  albedo = (0.7, 0.8, 1.0);  n = 0;  depth = 0;  hit = 0
+ *     feat0[p] = (sum albedo.rgb, sum hit)     feat1[p] = (sum n.xyz, sum depth)
+ * Each sum is a binary32 sum in ascending s that starts from the first sample's value: the order is
+ * part of the contract (one lane runs all samples of a pixel), so the buffers are bit-exact
+ * functions of the scene, the camera and the sample range.
+ *   feat0, feat1      DEVICE float4 arrays of band_width * band_height texels.
+ *   feature_samples   1 .. RT_FEATURE_MAX_SAMPLES; independent of the frame's samples per pixel
+ *                     (primary rays are cheap: 16 is a good default under 4-64 spp frames).
+ *   opt               rng_mode must be RT_RNG_SAMPLE_HASH and accumulate 0 (RT_ERR_INVALID_ARGUMENT
+ *                     otherwise); accel and the reserved words select the walk as for a frame;
+ *                     max_depth is unused.
+ * Asynchronous on `stream` like rt_render_device, without a host wait. A features launch is one
+ * launch for rt_launch_ms and rt_get_stats, but it neither reads nor updates the tile order, tile
+ * costs and row weights of the context's frames.
+ */
+#define RT_FEATURE_MAX_SAMPLES 256u
+int rt_render_features_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                              uint32_t band_width, uint32_t band_height, float* feat0, float* feat1,
+                              uint32_t feature_samples, const rt_options* opt, void* stream);
+/*
+ * Edge-avoiding a-trous denoise of a summed accumulator, guided by the feature buffers above
+ * (DESIGN.md §3.1.3). The band's rows must be contiguous image rows (there is no `rows` argument:
+ * the filter's taps are the band's own neighbours), band_width, band_height < 65536. Every operation
+ * is one correctly rounded binary32 + - x /, in this order (a restatement on the CPU gives the same
+ * bits, tests/denoise_sim.py):
+ *     n_p = sample_count ? sample_count[p] : spp;   c = n_p ? accum.rgb / float(n_p) : 0
+ *     a = feat0.rgb / float(F);  nrm = feat1.xyz / float(F);  z = feat1.w / float(F)
+ *     e_0 = c / (a + 2^-6)                                                   (per channel)
+ *     iteration i = 0 .. iterations - 1, step = 1 << i; taps dy = -2..2 (outer), dx = -2..2 (inner),
+ *     q = p + step * (dx, dy), taps outside the band skipped:
+ *         dn = nrm_p - nrm_q;  dn2 = (dn.x dn.x + dn.y dn.y) + dn.z dn.z
+ *         dz = (z_p - z_q) / (z_p + 1)
+ *         de = e_i(p) - e_i(q);  de2 = (de.x de.x + de.y de.y) + de.z de.z
+ *         x  = ((1 + k_normal dn2) (1 + k_depth (dz dz))) (1 + (k_color 4^i) de2)
+ *         w  = (K[|dy|] K[|dx|]) / (x x),   K = {3/8, 1/4, 1/16}
+ *         num += w e_i(q);  den += w                      (both from 0, taps in order)
+ *     e_{i+1}(p) = num / den
+ *     mean = e_I (a + 2^-6);  rgba8 = rt_resolve_rgba8 of (mean, 1) at spp 1
+ *   sample_count      optional DEVICE array of band_width * band_height uint32 (as
+ *                     rt_render_adaptive_device writes it); NULL: every texel has `spp` samples.
+ *   feat0, feat1, feature_samples   as rt_render_features_device wrote them.
+ *   params            NULL: {3, 4.0f, 16.0f, 1.0f}.
+ *   out_mean_rgba32f  optional DEVICE float4 array: (mean, 1) per texel; out_rgba8: required.
+ * One kernel per iteration on `stream`, nothing waits on the host; the two intermediate float4
+ * band buffers belong to the context and grow on demand (the growth of an existing buffer drains
+ * `stream` once). rt_denoise_check is the call's parameter check alone (host only, no device).
+ */
+typedef struct rt_denoise {
+    uint32_t iterations;               /* 1 .. 6 */
+    float k_normal, k_depth, k_color;  /* finite, >= 0 */
+} rt_denoise;
+int rt_denoise_check(const rt_denoise* params, uint32_t band_width, uint32_t band_height,
+                     uint32_t feature_samples);
+int rt_denoise_device(rt_context* ctx, const float* accum_rgba32f, const uint32_t* sample_count, uint32_t spp,
+                      const float* feat0, const float* feat1, uint32_t feature_samples, uint32_t band_width,
+                      uint32_t band_height, const rt_denoise* params, float* out_mean_rgba32f,
+                      uint8_t* out_rgba8, void* stream);
+
 /* ---- multi-device (one process, N GPUs, RCCL over xGMI) ----------------------------- */
 typedef struct rt_multi rt_multi;
 /* Devices 0 .. n-1, n = min(gpu_count, visible devices) (>= 1): one context and one stream per

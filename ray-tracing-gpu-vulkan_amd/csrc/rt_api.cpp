@@ -426,6 +426,7 @@ int rt_context_destroy(rt_context* ctx) {
     }
     if (ctx->d_spheres) (void)hipFree(ctx->d_spheres);
     if (ctx->fixed) (void)hipFree(ctx->fixed);
+    if (ctx->denoise.planes) (void)hipFree(ctx->denoise.planes);
     if (ctx->adaptive.planes) (void)hipFree(ctx->adaptive.planes);
     if (ctx->adaptive.tiles) (void)hipFree(ctx->adaptive.tiles);
     if (ctx->adaptive.state) (void)hipFree(ctx->adaptive.state);

@@ -137,6 +137,13 @@ struct rt_context {
     CostSnap snap[kSnaps];
     bool keep_snaps = false;   // set by the first rt_launch_row_weights (or rt_multi at N > 1):
                                // a one-device frame loop pays no copies it never reads
+    // rt_denoise_device (rt_features.cpp): three float4 band planes in one
+    // allocation, the two the iterations alternate between and the guide plane the first one stores
+    struct Denoise {
+        float* planes = nullptr;
+        uint64_t cap = 0;                        // texels per plane
+        uint32_t lds_max_step = 4;               // rt_denoise_host.h kLdsMaxStep; rt_debug_denoise_lds_steps
+    } denoise;
     // Adaptive frames (rt_render_adaptive_device) keep their own buffers, so they
     // leave `fixed` and `sched` alone.
     struct Adaptive {

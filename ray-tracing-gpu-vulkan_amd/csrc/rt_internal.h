@@ -146,7 +146,10 @@ enum : uint32_t { ACCEL_BRUTE = 1, ACCEL_LBVH_GLOBAL = 2, ACCEL_LBVH_LDS = 3, AC
 //           split into chunks on any lanes / GPUs in any order and the sum is the same bits.
 //   PROBE:  diagnostic (rt_debug_closest_hits): a unit is one given ray (TraceParams::probe_rays), whose
 //           closest hit is stored instead of shaded; no random stream and no image.
-enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2 };
+//   FEATURES: rt_render_features_device: a unit is all feature samples of one pixel, in ascending
+//           order on one lane; each sample is HASH's camera ray, ended at its closest hit, whose
+//           albedo, normal and depth are summed in binary32 (TraceParams::feat0 / feat1).
+enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2, MODE_FEATURES = 3 };
 
 // Top treelet of a tree too big for LDS (ACCEL_LBVH_TOP): the nodes of depth <= kTreeletDepth in
 // the tree's depth-first order, 2 float4 each, AB layout: A = (lo.x, lo.y, hi.x, hi.y),
@@ -272,6 +275,10 @@ struct TraceParams {
     // probe_rays is set): texel i = ly * band_w + lx of the band is ray i
     const float* probe_rays;       // band_w * band_h rays {ox, oy, oz, vx, vy, vz}, v before normalisation
     uint32_t* probe_out;           // per ray {winning sphere or 0xffffffff, bits of its t}
+    // FEATURES launches (rt_features.cpp; launch_trace picks the kernels' MODE_FEATURES instantiation
+    // when feat0 is set): per texel of the band, float4 sums over the unit's samples
+    float* feat0;                  // {sum albedo.rgb, sum hit}
+    float* feat1;                  // {sum n.xyz, sum depth}
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,

@@ -393,7 +393,17 @@ struct Path {
     double sx, sy, sz;     // STREAM: dvec3 sum
     uint32_t qx, qy, qz;   // HASH: fixed-point partial sum since the last flush
 };
-
+// FEATURES: the unit's binary32 sums, in sample order. A type of its own, so that the other modes'
+// Path, and with it their code, is what it was: the kernels declare PathOf<MODE>, the functions
+// take a Path&, and the FEATURES branches (if constexpr) see the whole object (feat_path).
+struct FeatPath : Path {
+    float far, fag, fab, fah;   // albedo.rgb, hit
+    float fnx, fny, fnz, fdz;   // n.xyz, depth
+};
+template <int MODE> struct PathType { typedef Path type; };
+template <> struct PathType<rt::MODE_FEATURES> { typedef FeatPath type; };
+template <int MODE> using PathOf = typename PathType<MODE>::type;
+__device__ __forceinline__ FeatPath& feat_path(Path& ps) { return static_cast<FeatPath&>(ps); }
 // Global load of a rarely taken branch, waited for at once. vmcnt counts loads and stores alike
 // (gfx9): a load left pending across a branch makes the compiler wait vmcnt(0) at the loop head
 // (the register is reused there), which then also waits for the pixel stores still in flight —
@@ -588,6 +598,14 @@ __device__ __forceinline__ void begin_unit(const rt::TraceParams& P, Path& ps, u
     ps.s = s0;
     ps.s_end = s1;
     ps.segs = 0;
+    if constexpr (MODE == rt::MODE_FEATURES) {
+        // -0 is the identity of binary32 addition (-0 + x = x for every x, a zero of either sign
+        // included), so each sum starts from its first sample's value
+        FeatPath& fp = feat_path(ps);
+        fp.far = fp.fag = fp.fab = fp.fah = -0.0f;
+        fp.fnx = fp.fny = fp.fnz = fp.fdz = -0.0f;
+        return;
+    }
     if (MODE == rt::MODE_HASH) {
         ps.qx = ps.qy = ps.qz = 0u;
     } else if (P.accumulate) {  // shader.rgen:53-55
@@ -745,6 +763,13 @@ __device__ __forceinline__ void store_pixel(const rt::TraceParams& P, const Path
 template <int MODE, bool LSUM>
 __device__ __forceinline__ void finish_unit(const rt::TraceParams& P, Path& ps) {
     if constexpr (MODE == rt::MODE_PROBE) return;   // the ray's record is already stored (shade_rec)
+    if constexpr (MODE == rt::MODE_FEATURES) {      // the pixel's two feature texels (shade_rec summed them)
+        const size_t texel = size_t(ps.px >> 16) * P.band_w + (ps.px & 0xffffu);
+        const FeatPath& fp = feat_path(ps);
+        reinterpret_cast<float4*>(P.feat0)[texel] = make_float4(fp.far, fp.fag, fp.fab, fp.fah);
+        reinterpret_cast<float4*>(P.feat1)[texel] = make_float4(fp.fnx, fp.fny, fp.fnz, fp.fdz);
+        return;
+    }
     if (MODE == rt::MODE_HASH && LSUM) {   // the unit's whole sum from LDS, once
         unsigned long long* s = lane_sum_slot();
         const unsigned long long x = s[0] + ps.qx, y = s[RT_TRACE_BLOCK] + ps.qy, z = s[2 * RT_TRACE_BLOCK] + ps.qz;
@@ -828,6 +853,8 @@ __device__ __forceinline__ bool start_sample(const rt::TraceParams& P, const Cam
         o = v3(q[0], q[1], q[2]);
         v = v3(q[3], q[4], q[5]);
         ps.depth = 0;
+    } else if constexpr (MODE == rt::MODE_FEATURES) {   // sample s of the pixel is HASH's camera ray
+        camera_ray<rt::MODE_HASH, FAST>(P, cam, ps, o, v);
     } else {
         camera_ray<MODE, FAST>(P, cam, ps, o, v);
     }
@@ -886,6 +913,35 @@ __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera
         P.probe_out[2 * i] = bi;
         P.probe_out[2 * i + 1] = __float_as_uint(best);
         return false;
+    }
+    if constexpr (MODE == rt::MODE_FEATURES) {
+        // the sample ends at its closest hit: its albedo, oriented normal and depth by the
+        // expressions of the shading below, added to the unit's sums; then the unit's next sample
+        V3 alb = v3(0.7f, 0.8f, 1.0f), n = v3(0.0f, 0.0f, 0.0f);   // shader.rmiss:15
+        float depth = 0.0f, hit = 0.0f;
+        if (bi != 0xffffffffu) {
+            const V3 p = v3(__builtin_fmaf(best, d.x, o.x), __builtin_fmaf(best, d.y, o.y),
+                            __builtin_fmaf(best, d.z, o.z));
+            const float4 m0 = hr.m0, m1 = hr.m1;
+            const uint32_t ttype = (__float_as_uint(m1.w) >> 8) & 0xffu;
+            const V3 outward = normalize(sub(p, v3(hr.g.x, hr.g.y, hr.g.z)));
+            const bool front = dot(d, outward) < 0.0f;
+            n = front ? outward : neg(outward);
+            alb = v3(m0.x, m0.y, m0.z);
+            if (ttype == 1u && !checker_positive(p.x, p.y, p.z)) alb = v3(m1.x, m1.y, m1.z);
+            depth = best;
+            hit = 1.0f;
+        }
+        FeatPath& fp = feat_path(ps);
+        fp.far += alb.x; fp.fag += alb.y; fp.fab += alb.z; fp.fah += hit;
+        fp.fnx += n.x; fp.fny += n.y; fp.fnz += n.z; fp.fdz += depth;
+        ps.s++;
+        if (ps.s >= ps.s_end) return false;
+        V3 v;
+        camera_ray<rt::MODE_HASH, FAST>(P, cam, ps, o, v);
+        d = normalize(v);
+        fresh = true;
+        return true;
     }
     V3 att;
     bool scatter = false;
@@ -989,7 +1045,7 @@ template <int MODE>
 __device__ __forceinline__ void record_tile_cost(const rt::TraceParams& P, const Path& ps) {
     // (P.tile_cost is set for every walk kernel, the only callers; a probe launch has none and leaves
     // the context's LPT record alone)
-    if constexpr (MODE == rt::MODE_PROBE) return;
+    if constexpr (MODE == rt::MODE_PROBE || MODE == rt::MODE_FEATURES) return;
     if (MODE == rt::MODE_HASH && (ps.px & 0x00010001u)) return;
     const uint32_t lx = ps.px & 0xffffu, ly = ps.px >> 16;
     uint32_t* c = &P.tile_cost[(ly >> 3) * P.tiles_x + (lx >> 3)];
@@ -1025,7 +1081,7 @@ __global__ __launch_bounds__(kBruteBlock, RT_BRUTE_WAVES_PER_SIMD) void rt_trace
     const uint32_t lane = lane_id();
     const Camera cam = load_camera(P);
     uint32_t st = ST_NEED_UNIT;
-    Path ps{};
+    PathOf<MODE> ps{};
     V3 o = v3(0, 0, 0), d = v3(0, 0, 1);
     uint32_t n_seg = 0, n_smp = 0, n_sph = 0;
     WaveBlock blk;
@@ -1864,7 +1920,7 @@ __device__ __forceinline__ void lbvh_loop(const rt::TraceParams& P, const float4
     const uint32_t lane = lane_id();
     const Camera cam = load_camera(P);
     uint32_t st = ST_NEED_UNIT;
-    Path ps{};
+    PathOf<MODE> ps{};
     Ray r{};
     if (LSUM) {   // this thread's unit sums (read and written by this thread only: no barrier)
         unsigned long long* s = lane_sum_slot();
@@ -2351,10 +2407,11 @@ static const void* pick_form(uint32_t accel, bool flat) {
 #undef RT_FN
 }
 
-// PROBE launches (rt_debug_closest_hits) are never instrumented: that mode has no COUNT kernels.
+// PROBE launches (rt_debug_closest_hits) and FEATURES launches (rt_render_features_device) are never
+// instrumented: those modes have no COUNT kernels.
 template <int MODE, int TAB>
 static const void* pick_mode(uint32_t accel, bool count, bool flat) {
-    if constexpr (MODE != MODE_PROBE) {
+    if constexpr (MODE != MODE_PROBE && MODE != MODE_FEATURES) {
         if (count) return pick_form<MODE, TAB, true>(accel, flat);
     }
     return pick_form<MODE, TAB, false>(accel, flat);
@@ -2362,6 +2419,7 @@ static const void* pick_mode(uint32_t accel, bool count, bool flat) {
 
 static const void* pick(uint32_t accel, bool count, int mode, bool flat, int tab = 0) {
     if (mode == MODE_PROBE) return pick_mode<MODE_PROBE, 0>(accel, false, flat);
+    if (mode == MODE_FEATURES) return pick_mode<MODE_FEATURES, 0>(accel, false, flat);
     if (mode != MODE_HASH) return pick_mode<MODE_STREAM, 0>(accel, count, flat);
     if (tab == 2) return pick_mode<MODE_HASH, 2>(accel, count, flat);
     return tab ? pick_mode<MODE_HASH, 1>(accel, count, flat) : pick_mode<MODE_HASH, 0>(accel, count, flat);
@@ -2379,8 +2437,10 @@ hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mo
                         hipStream_t st) {
     void* args[] = {const_cast<TraceParams*>(&P)};
     // (the table form's occupancy is its uniform twin's: the same launch bounds and LDS; a probe
-    // launch is planned as the STREAM launch of its band)
+    // launch is planned as the STREAM launch of its band, and so is a features launch: one unit per
+    // pixel holding all its samples)
     if (P.probe_rays) mode = MODE_PROBE;
+    if (P.feat0) mode = MODE_FEATURES;
     return hipLaunchKernel(pick(accel, count, mode, flat_grid_form(P, accel, count), P.block_tab ? (P.tab_size ? 2 : 1) : 0), dim3(grid),
                            dim3(block_size(accel)),
                            args, lds_bytes, st);

@@ -24,6 +24,11 @@
 //   --map-launch levels|one: the schedule of the replays (rt_sample_map_set_schedule): one trace
 //   launch per distinct count (default), or one launch of a block table for the whole frame.
 //   Refused without --replay; duration_per_frame names it.
+//   --denoise [F[,ITER]]: one frame on one GPU in the counter-based stream (--rng hash, or an
+//   --adaptive frame), then first-hit feature buffers of F samples per pixel (default 16,
+//   rt_render_features_device) and the edge-avoiding denoise of ITER iterations (default 3,
+//   rt_denoise_device); --store writes the denoised image. Refused with --gpus above 1, with
+//   --frames, and on the plain path without --rng hash.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -174,6 +179,63 @@ int run_adaptive(uint32_t samples, uint32_t width, uint32_t height, bool store, 
     return 0;
 }
 
+// One frame of the canonical scene on device 0, plain (ad == nullptr) or adaptive, then its feature
+// buffers and the denoise; the stored image is the denoised one.
+int run_denoised(uint32_t samples, uint32_t width, uint32_t height, bool store, const rt_adaptive* ad,
+                 uint32_t feature_samples, uint32_t iterations) {
+    rt_context* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    float *accum = nullptr, *feat0 = nullptr, *feat1 = nullptr;
+    uint8_t* rgba8 = nullptr;
+    uint32_t* counts = nullptr;
+    rt_denoise dn = {iterations, 4.0f, 16.0f, 1.0f};
+    const size_t texels = size_t(width) * height;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    CLI_HIP(hipMalloc(&accum, texels * 16));
+    CLI_HIP(hipMalloc(&feat0, texels * 16));
+    CLI_HIP(hipMalloc(&feat1, texels * 16));
+    CLI_HIP(hipMalloc(&rgba8, texels * 4));
+    if (ad) CLI_HIP(hipMalloc(&counts, texels * 4));
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0;
+    CLI_RT(rt_generate_scene(0.0f, 11, scene.data(), uint32_t(scene.size()), &cnt));
+    CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+    RenderCallInfo rci;
+    CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+    rt_options opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    rt_adaptive_info info;
+    std::memset(&info, 0, sizeof(info));
+    CLI_HIP(hipStreamSynchronize(stream));
+    const auto b = std::chrono::steady_clock::now();
+    if (ad) CLI_RT(rt_render_adaptive_device(ctx, &rci, nullptr, width, height, accum, rgba8, counts, &opt, ad, &info, stream));
+    else CLI_RT(rt_render_device(ctx, &rci, nullptr, width, height, accum, rgba8, &opt, stream));
+    CLI_RT(rt_render_features_device(ctx, &rci, nullptr, width, height, feat0, feat1, feature_samples, &opt, stream));
+    CLI_RT(rt_denoise_device(ctx, accum, counts, samples, feat0, feat1, feature_samples, width, height, &dn, nullptr, rgba8,
+                             stream));
+    CLI_HIP(hipStreamSynchronize(stream));
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+    const double spp = ad ? double(info.samples) / double(texels) : double(samples);
+    std::printf("duration_per_frame: %.3f ms (%s, mean %.2f spp, denoised: %u feature samples, %u iterations)\n", sec * 1e3,
+                ad ? "adaptive" : "plain", spp, feature_samples, iterations);
+    if (store) {
+        std::vector<uint8_t> img(texels * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    (void)hipFree(accum);
+    (void)hipFree(feat0);
+    (void)hipFree(feat1);
+    (void)hipFree(rgba8);
+    (void)hipFree(counts);
+    return 0;
+}
+
 // The frame loop with adaptive frames, on device 0: frame i is an adaptive frame when
 // i % (replay + 1) == 0, else a sample-map frame replaying the latest adaptive frame's counts. One
 // stream, the scene rebuilt per frame as run_frames does; the replays are queued without a host wait.
@@ -284,6 +346,14 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     return 0;
 }
 
+// F[,ITER]
+bool parse_denoise(const char* s, uint32_t& f, uint32_t& iter) {
+    const std::string v = s;
+    const size_t comma = v.find(',');
+    if (!parse_u32(v.substr(0, comma).c_str(), f)) return false;
+    return comma == std::string::npos || parse_u32(v.c_str() + comma + 1, iter);
+}
+
 // THRESHOLD[,MIN[,STEP]]
 bool parse_adaptive(const char* s, rt_adaptive& ad) {
     std::memset(&ad, 0, sizeof(ad));
@@ -309,7 +379,8 @@ int main(int argc, const char** argv) {
     uint32_t samples = 10, width = 1920, height = 1080, gpu_count = 1, frames = 0, rng_mode = RT_RNG_PIXEL_STREAM;
     uint32_t replay = 0, map_schedule = RT_SAMPLE_MAP_LEVELS;
     bool rng_explicit = false, replay_given = false, map_launch_given = false;
-    bool store = false, animate = false, adaptive = false, feedback = false;
+    bool store = false, animate = false, adaptive = false, feedback = false, denoise = false;
+    uint32_t feature_samples = 16, denoise_iterations = 3;
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
@@ -333,6 +404,9 @@ int main(int argc, const char** argv) {
             std::puts("--feedback                        # With --adaptive and --frames: every frame after the first renders");
             std::puts("                                  # the previous frame's map, measures its noise and plans the next");
             std::puts("                                  # map on the GPU (not with --replay)");
+            std::puts("--denoise [<F>[,<iter>]]          # One GPU, hash stream, one frame: first-hit features of F samples");
+            std::puts("                                  # per pixel (default 16), then iter edge-avoiding filter passes");
+            std::puts("                                  # (default 3); --store writes the denoised image");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -341,6 +415,15 @@ int main(int argc, const char** argv) {
             }
             ++i;
             adaptive = true;
+        } else if (a == "--denoise") {
+            denoise = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // the optional value
+                if (!parse_denoise(argv[i + 1], feature_samples, denoise_iterations)) {
+                    std::fprintf(stderr, "--denoise takes F[,ITER]\n");
+                    return 2;
+                }
+                ++i;
+            }
         } else if (a == "--store") {
             store = true;
         } else if (a == "--feedback") {
@@ -405,11 +488,31 @@ int main(int argc, const char** argv) {
             return 2;
         }
     }
+    if (denoise) {   // refused before anything renders
+        if (gpu_count > 1) {
+            std::fprintf(stderr, "--denoise runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
+            return 2;
+        }
+        if (frames > 0) {
+            std::fprintf(stderr, "--denoise renders one frame: it cannot run with --frames\n");
+            return 2;
+        }
+        if (!adaptive && !(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
+            std::fprintf(stderr, "--denoise needs the counter-based stream: give --rng hash (or --adaptive)\n");
+            return 2;
+        }
+        const rt_denoise dn = {denoise_iterations, 4.0f, 16.0f, 1.0f};
+        if (rt_denoise_check(&dn, width, height, feature_samples) != RT_OK) {
+            std::fprintf(stderr, "--denoise: %s\n", rt_last_error());
+            return 2;
+        }
+    }
     int n = 0;
     if (rt_device_count(&n) != RT_OK) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
+    if (denoise) return run_denoised(samples, width, height, store, adaptive ? &ad : nullptr, feature_samples, denoise_iterations);
     if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay, map_schedule, feedback);
     if (adaptive) return run_adaptive(samples, width, height, store, ad);
     if (frames > 0) return run_frames(samples, width, height, gpu_count, frames, animate, store, rng_mode);

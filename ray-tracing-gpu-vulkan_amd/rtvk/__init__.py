@@ -31,6 +31,7 @@ __all__ = [
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
     "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
+    "make_denoise", "denoise_check",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -90,6 +91,22 @@ def make_feedback(threshold: float, min_spp: int = 4, max_spp: int = 64, unit_sa
     f = abi.SampleMapFeedback()
     f.threshold, f.min_spp, f.max_spp, f.unit_samples, f.reserved = threshold, min_spp, max_spp, unit_samples, 0
     return f
+
+
+def make_denoise(iterations: int = 3, k_normal: float = 4.0, k_depth: float = 16.0,
+                 k_color: float = 1.0) -> "abi.Denoise":
+    """rt_denoise of Renderer.denoise: `iterations` a-trous passes (1..6, steps 1, 2, 4, ...), and the
+    edge-stopping strengths of the first-hit normal, the relative first-hit depth and the
+    demodulated colour (finite, >= 0; 0 switches a term off). The defaults are the library's."""
+    d = abi.Denoise()
+    d.iterations, d.k_normal, d.k_depth, d.k_color = iterations, k_normal, k_depth, k_color
+    return d
+
+
+def denoise_check(params: Optional["abi.Denoise"], band_w: int, band_h: int, feature_samples: int) -> None:
+    """rt_denoise_check (host only): raises RtError where Renderer.denoise would refuse."""
+    check(load_library().rt_denoise_check(ctypes.byref(params) if params is not None else None,
+                                          band_w, band_h, feature_samples))
 
 
 def threshold_q16(threshold: float) -> int:
@@ -367,6 +384,62 @@ class Renderer:
                                                              smap._map if smap is not None else None,
                                                              ctypes.byref(feedback) if feedback is not None else None,
                                                              err_ptr, _stream_ptr(stream, self.device)))
+
+    def render_features(self, rci: RenderCallInfo, feat0, feat1, samples: int = 16, rows=None,
+                        options: Optional[Options] = None, stream=None) -> None:
+        """First-hit feature buffers of one band (rt_render_features_device): feat0 = (sum albedo.rgb,
+        sum hit), feat1 = (sum n.xyz, sum depth) over the camera rays of samples [sample_base,
+        sample_base + samples) of the HASH stream, float32 cuda tensors [band_h, band_w, 4]. options
+        as render_device with rng_mode HASH (the default here) and accumulate off; rows as
+        render_device. Asynchronous on `stream`, no host wait."""
+        bh, bw = int(feat0.shape[0]), int(feat0.shape[1])
+        _check_dev_tensor(feat0, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(feat1, "torch.float32", (bh, bw, 4))
+        rows_ptr = None
+        if rows is not None:
+            if rows.numel() != bh or not rows.is_cuda or rows.element_size() != 4 or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous 4-byte cuda tensor of band_h entries")
+            rows_ptr = rows.data_ptr()
+        if options is None:
+            options = make_options(rng_mode=HASH)
+        check(self._lib.rt_render_features_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
+                                                  feat0.data_ptr(), feat1.data_ptr(), samples,
+                                                  ctypes.byref(options), _stream_ptr(stream, self.device)))
+
+    def denoise(self, accum, feat0, feat1, feature_samples: int, out, spp: Optional[int] = None,
+                sample_count=None, out_mean=None, params: Optional["abi.Denoise"] = None, stream=None) -> None:
+        """Edge-avoiding denoise of a summed accumulator (rt_denoise_device), guided by render_features'
+        buffers of `feature_samples` samples. accum, feat0, feat1: float32 cuda tensors [band_h,
+        band_w, 4] of contiguous image rows; out: uint8 [band_h, band_w, 4]; the texels' sample counts
+        are `spp` or the 4-byte integer cuda tensor sample_count [band_h, band_w] (exactly one of
+        them); out_mean: optional float32 [band_h, band_w, 4] receiving (mean, 1); params from
+        make_denoise() (None: the defaults). The outputs must not alias the inputs. Asynchronous on
+        `stream`; no host wait once the context's band buffers stand."""
+        bh, bw = int(accum.shape[0]), int(accum.shape[1])
+        for t in (accum, feat0, feat1):
+            _check_dev_tensor(t, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        if (spp is None) == (sample_count is None):
+            raise ValueError("give exactly one of spp and sample_count")
+        count_ptr = None
+        if sample_count is not None:
+            if not sample_count.is_cuda or sample_count.element_size() != 4 or sample_count.is_floating_point() \
+                    or not sample_count.is_contiguous() or tuple(sample_count.shape) != (bh, bw):
+                raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            count_ptr = sample_count.data_ptr()
+        mean_ptr = None
+        if out_mean is not None:
+            _check_dev_tensor(out_mean, "torch.float32", (bh, bw, 4))
+            mean_ptr = out_mean.data_ptr()
+        check(self._lib.rt_denoise_device(self._ctx, accum.data_ptr(), count_ptr, int(spp or 0),
+                                          feat0.data_ptr(), feat1.data_ptr(), feature_samples, bw, bh,
+                                          ctypes.byref(params) if params is not None else None,
+                                          mean_ptr, out.data_ptr(), _stream_ptr(stream, self.device)))
+
+    def denoise_lds_steps(self, max_step: int) -> None:
+        """Diagnostic (rt_debug_denoise_lds_steps): denoise iterations of step <= max_step (0, 1, 2
+        or 4, the default) stage their taps in LDS; the image does not depend on it."""
+        check(self._lib.rt_debug_denoise_lds_steps(self._ctx, max_step))
 
     def host_waits(self) -> int:
         """Host waits inside calls documented as queued without one (rt_debug_host_waits)."""

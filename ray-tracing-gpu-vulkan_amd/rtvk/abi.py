@@ -118,6 +118,14 @@ class SampleMapFeedback(ctypes.Structure):
                 ("unit_samples", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class Denoise(ctypes.Structure):
+    """rt_denoise (include/rt_mi355x.h)."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("k_normal", ctypes.c_float), ("k_depth", ctypes.c_float),
+                ("k_color", ctypes.c_float)]
+
+
+FEATURE_MAX_SAMPLES = 256    # RT_FEATURE_MAX_SAMPLES
+
 TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
                "unit_min_samples", "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule", "refill_reserve",
                "isolate_tiles", "sah_knobs")
@@ -162,6 +170,7 @@ assert ctypes.sizeof(RenderCallInfo) == 64 and RenderCallInfo.camera_dir.offset 
 assert ctypes.sizeof(Options) == 32
 assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and AdaptiveInfo.samples.offset == 16
 assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
+assert ctypes.sizeof(Denoise) == 16
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
 _P, _U32, _I, _U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
@@ -212,6 +221,10 @@ EXPORTS = {
     "rt_scatter_rows": (_I, [_P, _P, _P, _P, _U32, _U32, _U32, _P, _P, _P]),
     "rt_resolve_rgba8": (_I, [_P, _P, ctypes.c_uint64, _U32, _P, _P]),
     "rt_gather_rows": (_I, [_P, _P, _P, _U32, _U32, _U32, _P, _P]),
+    "rt_render_features_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _U32,
+                                       ctypes.POINTER(Options), _P]),
+    "rt_denoise_check": (_I, [ctypes.POINTER(Denoise), _U32, _U32, _U32]),
+    "rt_denoise_device": (_I, [_P, _P, _P, _U32, _P, _P, _U32, _U32, _U32, ctypes.POINTER(Denoise), _P, _P, _P]),
     "rt_multi_create": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_multi_destroy": (_I, [_P]),
     "rt_multi_device_count": (_I, [_P, ctypes.POINTER(_U32)]),
@@ -261,6 +274,7 @@ EXPORTS = {
     "rt_debug_multi_tune": (_I, [_P, ctypes.c_char_p, ctypes.c_double]),
     "rt_debug_multi_feedback": (_I, [_P, _P, _U32]),
     "rt_debug_multi_balance_info": (_I, [_P, _P]),
+    "rt_debug_denoise_lds_steps": (_I, [_P, _U32]),
 }
 
 _lib = None
