@@ -516,6 +516,54 @@ int rt_denoise_device(rt_context* ctx, const float* accum_rgba32f, const uint32_
                       const float* feat0, const float* feat1, uint32_t feature_samples, uint32_t band_width,
                       uint32_t band_height, const rt_denoise* params, float* out_mean_rgba32f,
                       uint8_t* out_rgba8, void* stream);
+/*
+ * Variance-guided denoise: the filter above with a colour weight scaled by a
+ * per-texel variance, estimated from two half-buffers of the frame and carried through the
+ * iterations, so that one setting serves noisy and nearly converged frames alike. accum_a and
+ * accum_b are two summed accumulators of the same band, each holding h_p samples of texel p:
+ * h_p = half_count ? half_count[p] : half_spp. A uniform frame of n = 2 h spp is two
+ * rt_render_device calls with samplesPerRenderCall = h under RT_RNG_SAMPLE_HASH, one at
+ * sample_base = b and one at sample_base = b + h; a sample-map frame is two
+ * rt_render_sample_map_device frames whose sample_base differ by the cap, and half_count is the
+ * sample_count plane either writes. Every operation is one correctly rounded binary32 + - x /, in
+ * this order (tests/denoise_var_sim.py gives the same bits); taps, their order and the borders are
+ * rt_denoise_device's, K = {3/8, 1/4, 1/16}:
+ *     hf = float(h_p);  ma = h_p ? A.rgb / hf : 0;  mb = h_p ? B.rgb / hf : 0
+ *     a = feat0.rgb / float(F) + 2^-6;  nrm = feat1.xyz / float(F);  z = feat1.w / float(F)
+ *     e_0 = ((ma + mb) * 0.5) / a                                            (per channel)
+ *     d   = (ma - mb) / a;   v_0 = 0.25 * ((d.x d.x + d.y d.y) + d.z d.z)
+ *     f(p, q) = (1 + k_normal dn2) (1 + k_depth (dz dz))      dn2, dz as in rt_denoise_device
+ *     prefilter pass j = 0 .. prefilter - 1, step = 1 << j (e unchanged):
+ *         w = (K[|dy|] K[|dx|]) / (f f);   nv += w v(q);   den += w
+ *         v'(p) = nv / den
+ *     iteration i = 0 .. iterations - 1, step = 1 << i, v_i the prefiltered variance at i = 0:
+ *         de = e_i(p) - e_i(q);  de2 = (de.x de.x + de.y de.y) + de.z de.z
+ *         x  = f (1 + k_color (de2 / (v_i(p) + 2^-20)))
+ *         w  = (K[|dy|] K[|dx|]) / (x x)
+ *         num += w e_i(q);  den += w;  nv += (w w) v_i(q)
+ *         e_{i+1}(p) = num / den;      v_{i+1}(p) = nv / (den den)
+ *     mean = e_I a;   rgba8 = rt_resolve_rgba8 of (mean, 1) at spp 1
+ * k_color is not scaled by 4^i: the tracked variance shrinks as the filter converges. The centre
+ * tap has x = 1, so den > 0.
+ *   half_count        optional DEVICE array of band_width * band_height uint32; NULL: half_spp.
+ *   params            NULL: {3, 2, 4.0f, 16.0f, 0.25f}.
+ *   out_mean_rgba32f  optional DEVICE float4 array: (mean, 1) per texel; out_rgba8: required.
+ * Refusals are rt_denoise_check's, and prefilter > 3. prefilter + iterations kernels on `stream`,
+ * nothing waits on the host; the band buffers are those of rt_denoise_device, with its one
+ * exception. rt_denoise_variance_check is the parameter check alone (host only).
+ */
+typedef struct rt_denoise_variance {
+    uint32_t iterations;               /* 1 .. 6 */
+    uint32_t prefilter;                /* 0 .. 3 feature-only passes over the variance */
+    float k_normal, k_depth, k_color;  /* finite, >= 0 */
+} rt_denoise_variance;
+int rt_denoise_variance_check(const rt_denoise_variance* params, uint32_t band_width, uint32_t band_height,
+                              uint32_t feature_samples);
+int rt_denoise_variance_device(rt_context* ctx, const float* accum_a, const float* accum_b,
+                               const uint32_t* half_count, uint32_t half_spp, const float* feat0,
+                               const float* feat1, uint32_t feature_samples, uint32_t band_width,
+                               uint32_t band_height, const rt_denoise_variance* params,
+                               float* out_mean_rgba32f, uint8_t* out_rgba8, void* stream);
 
 /* ---- multi-device (one process, N GPUs, RCCL over xGMI) ----------------------------- */
 typedef struct rt_multi rt_multi;

@@ -204,7 +204,8 @@ int rt_debug_multi_feedback(rt_multi* m, const float* device_ms, uint32_t n);
 /* {strip frames rendered since the partition was set up, re-deals, rows moved, predicted max / mean
  * device time after the last re-deal}. */
 int rt_debug_multi_balance_info(const rt_multi* m, double* out4);
-/* rt_denoise_device's kernel form (A/B and tests; the image does not depend on it): iterations of
+/* The kernel form of rt_denoise_device and of rt_denoise_variance_device, its prefilter passes
+ * included (A/B and tests; the image does not depend on it): iterations of
  * step <= max_step stage their taps in LDS, the others read them from global memory. 0 (every
  * iteration from global memory), 1, 2 or 4 (the default); other values: RT_ERR_INVALID_ARGUMENT. */
 int rt_debug_denoise_lds_steps(rt_context* ctx, uint32_t max_step);

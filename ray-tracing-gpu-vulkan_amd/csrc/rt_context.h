@@ -138,7 +138,8 @@ struct rt_context {
     bool keep_snaps = false;   // set by the first rt_launch_row_weights (or rt_multi at N > 1):
                                // a one-device frame loop pays no copies it never reads
     // rt_denoise_device (rt_features.cpp): three float4 band planes in one
-    // allocation, the two the iterations alternate between and the guide plane the first one stores
+    // allocation, the two the iterations alternate between and the guide plane the first one stores;
+    // rt_denoise_variance_device uses the same three (its variance rides in their w slot)
     struct Denoise {
         float* planes = nullptr;
         uint64_t cap = 0;                        // texels per plane

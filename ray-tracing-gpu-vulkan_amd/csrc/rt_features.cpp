@@ -5,7 +5,8 @@
 // sums a pixel's samples in ascending order. TraceParams::feat0 makes launch_trace pick the kernels'
 // MODE_FEATURES instantiation, which takes HASH's camera rays and ends each at its closest hit
 // (rt_kernels.hip shade_rec). The denoise is one kernel per iteration (rt_denoise.hip) by the launch
-// list of its HIP-free host half (rt_denoise_host.cpp).
+// list of its HIP-free host half (rt_denoise_host.cpp); the variance-guided denoise likewise
+// (rt_denoise_var.hip, rt_denoise_var_host.cpp), on the same band planes of the context.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -15,6 +16,8 @@
 #include "rt_context.h"
 #include "rt_denoise.h"
 #include "rt_denoise_host.h"
+#include "rt_denoise_var.h"
+#include "rt_denoise_var_host.h"
 #include "rt_launchers.h"
 
 using rt::fail;
@@ -136,6 +139,77 @@ extern "C" int rt_denoise_device(rt_context* ctx, const float* accum, const uint
             K.out_rgba8 = reinterpret_cast<uint32_t*>(out_rgba8);
         }
         RT_HIP(rt::launch_denoise(K, first, last, L.lds_step, st));
+    }
+    return rt::mark_issued(ctx, st);
+}
+
+extern "C" int rt_denoise_variance_check(const rt_denoise_variance* params, uint32_t band_width, uint32_t band_height,
+                                         uint32_t feature_samples) {
+    rt_denoise_variance p;
+    const char* err = "";
+    if (int rc = rt::denoise::check_variance(params, band_width, band_height, feature_samples, &p, &err))
+        return fail(rc, err);
+    return RT_OK;
+}
+
+extern "C" int rt_denoise_variance_device(rt_context* ctx, const float* accum_a, const float* accum_b,
+                                          const uint32_t* half_count, uint32_t half_spp, const float* feat0,
+                                          const float* feat1, uint32_t feature_samples, uint32_t band_width,
+                                          uint32_t band_height, const rt_denoise_variance* params, float* out_mean,
+                                          uint8_t* out_rgba8, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "ctx is NULL");
+    rt_denoise_variance p;
+    const char* err = "";
+    if (int rc = rt::denoise::check_variance(params, band_width, band_height, feature_samples, &p, &err))
+        return fail(rc, err);
+    if (band_width == 0 || band_height == 0) return RT_OK;
+    if (!accum_a || !accum_b || !feat0 || !feat1 || !out_rgba8)
+        return fail(RT_ERR_INVALID_ARGUMENT,
+                    "rt_denoise_variance_device: accum_a, accum_b, feat0, feat1 or out_rgba8 is NULL");
+    const uint64_t texels = uint64_t(band_width) * band_height;
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    rt_context::Denoise& dn = ctx->denoise;
+    if (p.prefilter + p.iterations > 1u && dn.cap < texels) {
+        if (dn.planes) ctx->host_waits++;   // queued denoises still read the old planes: the stream drains
+        if (int rc = rt::grow_on_stream(dn.planes, dn.cap, texels, 3u * 4u * sizeof(float), false, st)) return rc;
+    }
+    float* plane[3] = {nullptr, nullptr, nullptr};   // BUF_PING, BUF_PONG, the guide
+    if (dn.planes)
+        for (int k = 0; k < 3; k++) plane[k] = dn.planes + size_t(k) * dn.cap * 4u;
+    rt::denoise::VarLaunch list[rt::denoise::kMaxVarLaunches];
+    const uint32_t n = rt::denoise::plan_variance(p, dn.lds_max_step, list);
+    for (uint32_t i = 0; i < n; i++) {
+        const rt::denoise::VarLaunch& L = list[i];
+        rt::DenoiseVarParams K;
+        std::memset(&K, 0, sizeof(K));
+        K.band_w = band_width;
+        K.band_h = band_height;
+        K.step = L.step;
+        K.half_spp = half_spp;
+        K.feature_samples = float(feature_samples);
+        K.k_normal = p.k_normal;
+        K.k_depth = p.k_depth;
+        K.k_color = p.k_color;
+        K.accum_a = accum_a;
+        K.accum_b = accum_b;
+        K.half_count = half_count;
+        K.feat0 = feat0;
+        K.feat1 = feat1;
+        const bool first = L.src == rt::denoise::BUF_CALLER, last = L.dst == rt::denoise::BUF_CALLER;
+        if (!first) {
+            K.src = plane[L.src - 1u];
+            K.guide = plane[2];
+        }
+        if (!last) {
+            K.dst = plane[L.dst - 1u];
+            K.guide_out = plane[2];
+        } else {
+            K.out_mean = out_mean;
+            K.out_rgba8 = reinterpret_cast<uint32_t*>(out_rgba8);
+        }
+        RT_HIP(rt::launch_denoise_var(K, L.prefilter != 0u, first, last, L.lds_step, st));
     }
     return rt::mark_issued(ctx, st);
 }

@@ -29,6 +29,12 @@
 //   rt_render_features_device) and the edge-avoiding denoise of ITER iterations (default 3,
 //   rt_denoise_device); --store writes the denoised image. Refused with --gpus above 1, with
 //   --frames, and on the plain path without --rng hash.
+//   --denoise-variance [F[,ITER[,PRE]]]: one frame on one GPU in the counter-based stream (--rng
+//   hash) rendered as two halves of --samples / 2 (rt_render_device at sample_base 0 and
+//   --samples / 2), then the feature buffers of F samples and the variance-guided denoise of PRE
+//   prefilter passes (default 2) and ITER iterations (default 3, rt_denoise_variance_device);
+//   --store writes the denoised image. Takes --denoise's refusals, and refuses an odd --samples,
+//   --adaptive, and --denoise beside it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -236,6 +242,64 @@ int run_denoised(uint32_t samples, uint32_t width, uint32_t height, bool store, 
     return 0;
 }
 
+// One frame of the canonical scene on device 0 as two halves of samples / 2, then its feature
+// buffers and the variance-guided denoise; the stored image is the denoised one.
+int run_denoised_variance(uint32_t samples, uint32_t width, uint32_t height, bool store, uint32_t feature_samples,
+                          const rt_denoise_variance& dn) {
+    rt_context* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    float *accum_a = nullptr, *accum_b = nullptr, *feat0 = nullptr, *feat1 = nullptr;
+    uint8_t* rgba8 = nullptr;
+    const size_t texels = size_t(width) * height;
+    const uint32_t half = samples / 2u;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    CLI_HIP(hipMalloc(&accum_a, texels * 16));
+    CLI_HIP(hipMalloc(&accum_b, texels * 16));
+    CLI_HIP(hipMalloc(&feat0, texels * 16));
+    CLI_HIP(hipMalloc(&feat1, texels * 16));
+    CLI_HIP(hipMalloc(&rgba8, texels * 4));
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0;
+    CLI_RT(rt_generate_scene(0.0f, 11, scene.data(), uint32_t(scene.size()), &cnt));
+    CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+    RenderCallInfo rci, half_rci;
+    CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+    half_rci = rci;
+    half_rci.samplesPerRenderCall = half;
+    rt_options opt;
+    std::memset(&opt, 0, sizeof(opt));
+    opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    rt_options second = opt;
+    second.sample_base = half;
+    CLI_HIP(hipStreamSynchronize(stream));
+    const auto b = std::chrono::steady_clock::now();
+    CLI_RT(rt_render_device(ctx, &half_rci, nullptr, width, height, accum_a, rgba8, &opt, stream));
+    CLI_RT(rt_render_device(ctx, &half_rci, nullptr, width, height, accum_b, rgba8, &second, stream));
+    CLI_RT(rt_render_features_device(ctx, &rci, nullptr, width, height, feat0, feat1, feature_samples, &opt, stream));
+    CLI_RT(rt_denoise_variance_device(ctx, accum_a, accum_b, nullptr, half, feat0, feat1, feature_samples, width, height,
+                                      &dn, nullptr, rgba8, stream));
+    CLI_HIP(hipStreamSynchronize(stream));
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+    std::printf("duration_per_frame: %.3f ms (two halves of %u spp, variance-guided denoise: %u feature samples, "
+                "%u prefilter passes, %u iterations)\n",
+                sec * 1e3, half, feature_samples, dn.prefilter, dn.iterations);
+    if (store) {
+        std::vector<uint8_t> img(texels * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    (void)hipFree(accum_a);
+    (void)hipFree(accum_b);
+    (void)hipFree(feat0);
+    (void)hipFree(feat1);
+    (void)hipFree(rgba8);
+    return 0;
+}
+
 // The frame loop with adaptive frames, on device 0: frame i is an adaptive frame when
 // i % (replay + 1) == 0, else a sample-map frame replaying the latest adaptive frame's counts. One
 // stream, the scene rebuilt per frame as run_frames does; the replays are queued without a host wait.
@@ -354,6 +418,17 @@ bool parse_denoise(const char* s, uint32_t& f, uint32_t& iter) {
     return comma == std::string::npos || parse_u32(v.c_str() + comma + 1, iter);
 }
 
+// F[,ITER[,PRE]]
+bool parse_denoise_variance(const char* s, uint32_t& f, uint32_t& iter, uint32_t& pre) {
+    const std::string v = s;
+    const size_t c1 = v.find(',');
+    if (!parse_u32(v.substr(0, c1).c_str(), f)) return false;
+    if (c1 == std::string::npos) return true;
+    const size_t c2 = v.find(',', c1 + 1);
+    if (!parse_u32(v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1).c_str(), iter)) return false;
+    return c2 == std::string::npos || parse_u32(v.c_str() + c2 + 1, pre);
+}
+
 // THRESHOLD[,MIN[,STEP]]
 bool parse_adaptive(const char* s, rt_adaptive& ad) {
     std::memset(&ad, 0, sizeof(ad));
@@ -381,6 +456,9 @@ int main(int argc, const char** argv) {
     bool rng_explicit = false, replay_given = false, map_launch_given = false;
     bool store = false, animate = false, adaptive = false, feedback = false, denoise = false;
     uint32_t feature_samples = 16, denoise_iterations = 3;
+    bool denoise_variance = false;
+    uint32_t dv_feature_samples = 16;
+    rt_denoise_variance dv = {3u, 2u, 4.0f, 16.0f, 0.25f};
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
@@ -407,6 +485,9 @@ int main(int argc, const char** argv) {
             std::puts("--denoise [<F>[,<iter>]]          # One GPU, hash stream, one frame: first-hit features of F samples");
             std::puts("                                  # per pixel (default 16), then iter edge-avoiding filter passes");
             std::puts("                                  # (default 3); --store writes the denoised image");
+            std::puts("--denoise-variance [<F>[,<iter>[,<pre>]]]  # One GPU, hash stream, one frame of an even sample count as");
+            std::puts("                                  # two halves, features of F samples, then the variance-guided filter:");
+            std::puts("                                  # pre prefilter passes (default 2), iter iterations (default 3)");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -420,6 +501,15 @@ int main(int argc, const char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // the optional value
                 if (!parse_denoise(argv[i + 1], feature_samples, denoise_iterations)) {
                     std::fprintf(stderr, "--denoise takes F[,ITER]\n");
+                    return 2;
+                }
+                ++i;
+            }
+        } else if (a == "--denoise-variance") {
+            denoise_variance = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // the optional value
+                if (!parse_denoise_variance(argv[i + 1], dv_feature_samples, dv.iterations, dv.prefilter)) {
+                    std::fprintf(stderr, "--denoise-variance takes F[,ITER[,PRE]]\n");
                     return 2;
                 }
                 ++i;
@@ -488,6 +578,36 @@ int main(int argc, const char** argv) {
             return 2;
         }
     }
+    if (denoise_variance) {   // refused before anything renders
+        if (denoise) {
+            std::fprintf(stderr, "--denoise-variance is a filter of its own: it cannot run with --denoise\n");
+            return 2;
+        }
+        if (adaptive) {
+            std::fprintf(stderr, "--denoise-variance renders two plain halves: it cannot run with --adaptive\n");
+            return 2;
+        }
+        if (gpu_count > 1) {
+            std::fprintf(stderr, "--denoise-variance runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
+            return 2;
+        }
+        if (frames > 0) {
+            std::fprintf(stderr, "--denoise-variance renders one frame: it cannot run with --frames\n");
+            return 2;
+        }
+        if (!(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
+            std::fprintf(stderr, "--denoise-variance needs the counter-based stream: give --rng hash\n");
+            return 2;
+        }
+        if (samples % 2u) {
+            std::fprintf(stderr, "--denoise-variance splits the frame in two halves: --samples %u is odd\n", samples);
+            return 2;
+        }
+        if (rt_denoise_variance_check(&dv, width, height, dv_feature_samples) != RT_OK) {
+            std::fprintf(stderr, "--denoise-variance: %s\n", rt_last_error());
+            return 2;
+        }
+    }
     if (denoise) {   // refused before anything renders
         if (gpu_count > 1) {
             std::fprintf(stderr, "--denoise runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
@@ -512,6 +632,7 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
+    if (denoise_variance) return run_denoised_variance(samples, width, height, store, dv_feature_samples, dv);
     if (denoise) return run_denoised(samples, width, height, store, adaptive ? &ad : nullptr, feature_samples, denoise_iterations);
     if (adaptive && frames > 0) return run_adaptive_frames(samples, width, height, frames, animate, store, ad, replay, map_schedule, feedback);
     if (adaptive) return run_adaptive(samples, width, height, store, ad);

@@ -31,7 +31,7 @@ __all__ = [
     "Adaptive", "AdaptiveInfo", "make_adaptive", "threshold_q16", "adaptive_tile_converged",
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
     "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
-    "make_denoise", "denoise_check",
+    "make_denoise", "denoise_check", "make_denoise_variance", "denoise_variance_check",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -107,6 +107,25 @@ def denoise_check(params: Optional["abi.Denoise"], band_w: int, band_h: int, fea
     """rt_denoise_check (host only): raises RtError where Renderer.denoise would refuse."""
     check(load_library().rt_denoise_check(ctypes.byref(params) if params is not None else None,
                                           band_w, band_h, feature_samples))
+
+
+def make_denoise_variance(iterations: int = 3, prefilter: int = 2, k_normal: float = 4.0, k_depth: float = 16.0,
+                          k_color: float = 0.25) -> "abi.DenoiseVariance":
+    """rt_denoise_variance of Renderer.denoise_variance: `prefilter` feature-only passes over the
+    half-buffer variance (0..3), then `iterations` a-trous passes (1..6) whose colour weight is
+    k_color times the squared colour difference over the tracked variance. The defaults are the
+    library's."""
+    d = abi.DenoiseVariance()
+    d.iterations, d.prefilter, d.k_normal, d.k_depth, d.k_color = iterations, prefilter, k_normal, k_depth, k_color
+    return d
+
+
+def denoise_variance_check(params: Optional["abi.DenoiseVariance"], band_w: int, band_h: int,
+                           feature_samples: int) -> None:
+    """rt_denoise_variance_check (host only): raises RtError where Renderer.denoise_variance would
+    refuse."""
+    check(load_library().rt_denoise_variance_check(ctypes.byref(params) if params is not None else None,
+                                                   band_w, band_h, feature_samples))
 
 
 def threshold_q16(threshold: float) -> int:
@@ -435,6 +454,59 @@ class Renderer:
                                           feat0.data_ptr(), feat1.data_ptr(), feature_samples, bw, bh,
                                           ctypes.byref(params) if params is not None else None,
                                           mean_ptr, out.data_ptr(), _stream_ptr(stream, self.device)))
+
+    def denoise_variance(self, accum_a, accum_b, feat0, feat1, feature_samples: int, out,
+                         half_spp: Optional[int] = None, half_count=None, out_mean=None,
+                         params: Optional["abi.DenoiseVariance"] = None, stream=None) -> None:
+        """Variance-guided denoise of a frame rendered as two halves (rt_denoise_variance_device):
+        accum_a and accum_b are the halves' summed accumulators (render_halves, or two sample-map
+        frames), each texel holding `half_spp` samples or those of the 4-byte integer cuda tensor
+        half_count [band_h, band_w] (exactly one of them). The other tensors, params
+        (make_denoise_variance(); None: the defaults) and the stream are as for denoise."""
+        bh, bw = int(accum_a.shape[0]), int(accum_a.shape[1])
+        for t in (accum_a, accum_b, feat0, feat1):
+            _check_dev_tensor(t, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        if (half_spp is None) == (half_count is None):
+            raise ValueError("give exactly one of half_spp and half_count")
+        count_ptr = None
+        if half_count is not None:
+            if not half_count.is_cuda or half_count.element_size() != 4 or half_count.is_floating_point() \
+                    or not half_count.is_contiguous() or tuple(half_count.shape) != (bh, bw):
+                raise ValueError("half_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            count_ptr = half_count.data_ptr()
+        mean_ptr = None
+        if out_mean is not None:
+            _check_dev_tensor(out_mean, "torch.float32", (bh, bw, 4))
+            mean_ptr = out_mean.data_ptr()
+        check(self._lib.rt_denoise_variance_device(self._ctx, accum_a.data_ptr(), accum_b.data_ptr(), count_ptr,
+                                                   int(half_spp or 0), feat0.data_ptr(), feat1.data_ptr(),
+                                                   feature_samples, bw, bh,
+                                                   ctypes.byref(params) if params is not None else None,
+                                                   mean_ptr, out.data_ptr(), _stream_ptr(stream, self.device)))
+
+    def render_halves(self, rci: RenderCallInfo, accum_a, accum_b, out, rows=None,
+                      options: Optional[Options] = None, stream=None) -> None:
+        """A frame of rci.samplesPerRenderCall = 2 h samples per pixel as the two halves
+        denoise_variance reads: two render_device calls of h samples, accum_a at options.sample_base
+        and accum_b at sample_base + h, in the HASH stream (the default options; anything else is a
+        ValueError), so accum_a + accum_b holds the samples of the one frame. `out` receives the
+        second half's bytes and is scratch."""
+        n = int(rci.samplesPerRenderCall)
+        if n % 2:
+            raise ValueError("render_halves needs an even samplesPerRenderCall")
+        if options is None:
+            options = make_options(rng_mode=HASH)
+        if options.rng_mode != HASH:
+            raise ValueError("render_halves needs the counter-based stream (rng_mode HASH)")
+        if options.accumulate:
+            raise ValueError("render_halves does not accumulate")
+        half = RenderCallInfo.from_buffer_copy(bytes(rci))
+        half.samplesPerRenderCall = n // 2
+        second = Options.from_buffer_copy(bytes(options))
+        second.sample_base = options.sample_base + n // 2
+        self.render_device(half, accum_a, out, rows=rows, options=options, stream=stream)
+        self.render_device(half, accum_b, out, rows=rows, options=second, stream=stream)
 
     def denoise_lds_steps(self, max_step: int) -> None:
         """Diagnostic (rt_debug_denoise_lds_steps): denoise iterations of step <= max_step (0, 1, 2

@@ -124,6 +124,12 @@ class Denoise(ctypes.Structure):
                 ("k_color", ctypes.c_float)]
 
 
+class DenoiseVariance(ctypes.Structure):
+    """rt_denoise_variance (include/rt_mi355x.h)."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("prefilter", ctypes.c_uint32), ("k_normal", ctypes.c_float),
+                ("k_depth", ctypes.c_float), ("k_color", ctypes.c_float)]
+
+
 FEATURE_MAX_SAMPLES = 256    # RT_FEATURE_MAX_SAMPLES
 
 TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
@@ -171,6 +177,7 @@ assert ctypes.sizeof(Options) == 32
 assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and AdaptiveInfo.samples.offset == 16
 assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
 assert ctypes.sizeof(Denoise) == 16
+assert ctypes.sizeof(DenoiseVariance) == 20
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
 _P, _U32, _I, _U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
@@ -225,6 +232,9 @@ EXPORTS = {
                                        ctypes.POINTER(Options), _P]),
     "rt_denoise_check": (_I, [ctypes.POINTER(Denoise), _U32, _U32, _U32]),
     "rt_denoise_device": (_I, [_P, _P, _P, _U32, _P, _P, _U32, _U32, _U32, ctypes.POINTER(Denoise), _P, _P, _P]),
+    "rt_denoise_variance_check": (_I, [ctypes.POINTER(DenoiseVariance), _U32, _U32, _U32]),
+    "rt_denoise_variance_device": (_I, [_P, _P, _P, _P, _U32, _P, _P, _U32, _U32, _U32,
+                                        ctypes.POINTER(DenoiseVariance), _P, _P, _P]),
     "rt_multi_create": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_multi_destroy": (_I, [_P]),
     "rt_multi_device_count": (_I, [_P, ctypes.POINTER(_U32)]),
