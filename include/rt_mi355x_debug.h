@@ -152,6 +152,23 @@ int rt_debug_scene(rt_context* ctx, uint32_t what, void* out, uint64_t capacity,
  * conservative culling, the same answers) until its next rt_set_scene. */
 int rt_debug_closest_hits(rt_context* ctx, const float* rays6, uint32_t n, const rt_options* options,
                           uint32_t* out_id, float* out_t);
+/* Diagnostic (tests): one bounce of n given hits in ctx's scene by the frames' own shading code (the
+ * function every hit of a frame is shaded by), a lane per case. Case i: host ray rays6[6 i ..] = {ox,
+ * oy, oz, vx, vy, vz}, traced along the kernels' d = normalize(v), hit sphere ids[i] at t[i] with the
+ * LCG (random.glsl) in state seeds[i]. Outputs, host arrays: out_p[3 i ..] the hit point fma(t, d, o),
+ * out_att the attenuation, out_sd the scatter direction as the shader leaves it, out_dnext the
+ * direction the next segment of a frame would be traced along (normalize of it; zeros when the bounce
+ * does not scatter), out_scatter[i] 1 / 0, out_seed[i] the LCG state after the bounce. form: where the
+ * sphere's records come from, 0 the scene's global arrays (the tree, brute and L2 grid kernels'
+ * load), 1 the static LDS record table staged as the REC grid kernels stage it (scenes of at most
+ * 512 spheres). RT_ERR_INVALID_ARGUMENT: a NULL array, a ray value or t that is not finite, a
+ * direction without a nonzero component, ids[i] >= the scene's spheres, n above 2^24, an unknown form
+ * or form 1 on a larger scene. n = 0: RT_OK, nothing written; RT_ERR_NO_SCENE before rt_set_scene.
+ * Synchronous. Goes through no launch plan: frames, the tile-cost record and the hand-out order of
+ * the frames around it are left alone, and rt_debug_launch_info still describes the last frame. */
+int rt_debug_scatter(rt_context* ctx, const float* rays6, const uint32_t* ids, const float* t, const uint32_t* seeds,
+                     uint32_t n, uint32_t form, float* out_p, float* out_att, float* out_sd, float* out_dnext,
+                     uint32_t* out_scatter, uint32_t* out_seed);
 
 /*
  * The multi-device frame plan rt_multi_render (band_starts NULL: its first frame's row-exact strips,

@@ -52,6 +52,8 @@ def lib() -> ctypes.CDLL:
         l.orc_closest_hits.argtypes = [_P, _U, _P, _U, _I, _P, _P, _I]
         l.orc_report_t.restype = _I
         l.orc_report_t.argtypes = [_P, _U, _P, _U, _P, _P]
+        l.orc_scatter.restype = _I
+        l.orc_scatter.argtypes = [_P, _U, _P, _P, _P, _P, _U, _P, _P, _P, _P, _P, _P]
         l.orc_resolve.restype = _I
         l.orc_resolve.argtypes = [_P, ctypes.c_uint64, _U, _P]
         _lib = l
@@ -171,6 +173,27 @@ def report_t(spheres, rays, ids) -> np.ndarray:
     t = np.zeros(r.shape[0], np.float32)
     assert lib().orc_report_t(sp.ctypes.data, sp.size // 80, r.ctypes.data, r.shape[0], k.ctypes.data, t.ctypes.data) == 0
     return t
+
+
+def scatter(spheres, rays, ids, t, seeds) -> dict:
+    """One bounce of each case: ray i of `rays` [n, 6] = (o, v), traced along normalize(v), hit sphere
+    ids[i] at t[i] with the LCG in state seeds[i]. Returns {"p", "att", "sd" (the raw scatter
+    direction), "d_next" (normalize of it, zeros without a scatter): float32 [n, 3]; "scatter",
+    "seed": uint32 [n]}."""
+    sp = _as_u8(spheres)
+    r = np.ascontiguousarray(rays, np.float32)
+    k = np.ascontiguousarray(ids, np.uint32)
+    tt = np.ascontiguousarray(t, np.float32)
+    sd = np.ascontiguousarray(seeds, np.uint32)
+    n = r.shape[0]
+    assert r.ndim == 2 and r.shape[1] == 6 and k.shape == (n,) and tt.shape == (n,) and sd.shape == (n,)
+    out = {name: np.zeros((n, 3), np.float32) for name in ("p", "att", "sd", "d_next")}
+    out["scatter"] = np.zeros(n, np.uint32)
+    out["seed"] = np.zeros(n, np.uint32)
+    rc = lib().orc_scatter(sp.ctypes.data, sp.size // 80, r.ctypes.data, k.ctypes.data, tt.ctypes.data, sd.ctypes.data,
+                           n, *(out[name].ctypes.data for name in ("p", "att", "sd", "d_next", "scatter", "seed")))
+    assert rc == 0
+    return out
 
 
 def resolve(accum: np.ndarray, spp: int) -> np.ndarray:

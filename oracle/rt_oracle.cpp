@@ -23,7 +23,9 @@
  * SURVEY.md §4, both produced from the reference's own code (random.glsl restated in C and
  * Python; scene.h compiled by g++ during the survey). Traversal and shading arithmetic have no
  * reference fixture (the reference has no tests and its GLSL cannot run here): that part of the
- * oracle is "parity unpinned" against the reference and pinned only by this restatement.
+ * oracle is "parity unpinned" against the reference and pinned only by this restatement, which
+ * tests/test_oracle.py holds against independent float64 restatements: the closest hit against the
+ * plain quadratic, one bounce of every material against shader.rchit.
  *
  * ARITHMETIC CONTRACT — shared with the HIP kernels, each side implemented
  * independently:
@@ -683,6 +685,42 @@ int orc_report_t(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t
         float t;
         const bool real = report_t<LIT_CONTRACT>(spheres[ids[i]].geometry, v3(q[0], q[1], q[2]), d, a, 1.0f / a, &t);
         out_t[i] = real ? t : std::numeric_limits<float>::quiet_NaN();
+    }
+    return 0;
+}
+
+// One bounce of n_cases given hits (checker of rt_debug_scatter): case i is ray i of rays6, traced
+// along d = normalize(v), which hit sphere ids[i] at t[i] with the LCG in state seeds[i]. The hit
+// point is p = fma(t, d, o) and the bounce closest_hit_shader's, as ray_color runs them. Outputs per
+// case: p, the attenuation, the scatter direction as the shader leaves it, the direction the next
+// segment would be traced along (normalize of it; zeros without a scatter), does_scatter, and the
+// LCG state after the bounce. Returns -1 for an id beyond the scene.
+int orc_scatter(const Sphere* spheres, uint32_t n, const float* rays6, const uint32_t* ids, const float* t,
+                const uint32_t* seeds, uint32_t n_cases, float* out_p, float* out_att, float* out_sd,
+                float* out_dnext, uint32_t* out_scatter, uint32_t* out_seed) {
+    if (n_cases == 0) return 0;
+    if (!spheres || !rays6 || !ids || !t || !seeds || !out_p || !out_att || !out_sd || !out_dnext || !out_scatter ||
+        !out_seed)
+        return -1;
+    for (uint32_t i = 0; i < n_cases; i++) {
+        if (ids[i] >= n) return -1;
+        const float* q = rays6 + 6u * size_t(i);
+        const V3 o = v3(q[0], q[1], q[2]);
+        const V3 d = normalize<LIT_CONTRACT>(v3(q[3], q[4], q[5]));
+        const V3 p = v3(std::fma(t[i], d.x, o.x), std::fma(t[i], d.y, o.y), std::fma(t[i], d.z, o.z));
+        uint32_t seed = seeds[i];
+        Payload pl;
+        closest_hit_shader<LIT_CONTRACT>(spheres[ids[i]], p, d, seed, pl);
+        const V3 dn = pl.does_scatter ? normalize<LIT_CONTRACT>(pl.scatter_dir) : v3(0.0f, 0.0f, 0.0f);
+        const V3* vs[4] = {&pl.point, &pl.attenuation, &pl.scatter_dir, &dn};
+        float* outs[4] = {out_p, out_att, out_sd, out_dnext};
+        for (int k = 0; k < 4; k++) {
+            outs[k][3u * size_t(i)] = vs[k]->x;
+            outs[k][3u * size_t(i) + 1u] = vs[k]->y;
+            outs[k][3u * size_t(i) + 2u] = vs[k]->z;
+        }
+        out_scatter[i] = pl.does_scatter ? 1u : 0u;
+        out_seed[i] = seed;
     }
     return 0;
 }

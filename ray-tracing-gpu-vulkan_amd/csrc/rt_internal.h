@@ -149,7 +149,10 @@ enum : uint32_t { ACCEL_BRUTE = 1, ACCEL_LBVH_GLOBAL = 2, ACCEL_LBVH_LDS = 3, AC
 //   FEATURES: rt_render_features_device: a unit is all feature samples of one pixel, in ascending
 //           order on one lane; each sample is HASH's camera ray, ended at its closest hit, whose
 //           albedo, normal and depth are summed in binary32 (TraceParams::feat0 / feat1).
-enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2, MODE_FEATURES = 3 };
+//   SCATTER: diagnostic (rt_debug_scatter): STREAM's shading of one given hit, whose bounce is stored
+//           where a frame goes on to its next segment (rt_kernels.hip rt_scatter_probe_kernel; never a
+//           trace kernel's mode).
+enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2, MODE_FEATURES = 3, MODE_SCATTER = 4 };
 
 // Top treelet of a tree too big for LDS (ACCEL_LBVH_TOP): the nodes of depth <= kTreeletDepth in
 // the tree's depth-first order, 2 float4 each, AB layout: A = (lo.x, lo.y, hi.x, hi.y),
@@ -279,6 +282,21 @@ struct TraceParams {
     // when feat0 is set): per texel of the band, float4 sums over the unit's samples
     float* feat0;                  // {sum albedo.rgb, sum hit}
     float* feat1;                  // {sum n.xyz, sum depth}
+};
+
+// Parameters of the one-bounce diagnostic (rt_kernels.hip rt_scatter_probe_kernel, rt_probe_scatter.cpp).
+struct ScatterProbeParams {
+    uint32_t n_spheres;
+    const GeomRec* geom;
+    const float* radius;
+    const MatRec* mat;
+    uint32_t n;                    // cases
+    const float* rays;             // n rays {ox, oy, oz, vx, vy, vz}, v before normalisation
+    const uint32_t* ids;           // the sphere each ray hit (< n_spheres)
+    const float* t;                // and where
+    const uint32_t* seeds;         // LCG state before the bounce
+    uint32_t* out;                 // 14 words per case: p, attenuation, scatter direction, next direction
+                                   // (3 floats each, as bits), does_scatter, LCG state afterwards
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,

@@ -1003,6 +1003,25 @@ __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera
         }
         scatter = !(sd.x == 0.0f && sd.y == 0.0f && sd.z == 0.0f);  // shader.rchit:48
     }
+    if constexpr (MODE == rt::MODE_SCATTER) {   // the bounce itself is the answer: stored, the unit ends
+        // Up to and including this branch the MODE_SCATTER path may read nothing of P but probe_out and
+        // nothing of cam: rt_scatter_probe_kernel passes a zeroed TraceParams and Camera. (The UTIL
+        // points above count into s_util, which that kernel neither clears nor flushes: a -DRT_UTIL
+        // build's figures describe the trace kernels only.)
+        // case ps.px (rt_scatter_probe_kernel): p, the attenuation, the scatter direction as left
+        // above, the direction the next segment is traced along below, does_scatter, the LCG state
+        const V3 dn = scatter ? normalize(sd) : v3(0.0f, 0.0f, 0.0f);
+        uint32_t* w = P.probe_out + 14u * size_t(ps.px);
+        const V3 vs[4] = {p, att, sd, dn};
+        for (int k = 0; k < 4; k++) {
+            w[3 * k] = __float_as_uint(vs[k].x);
+            w[3 * k + 1] = __float_as_uint(vs[k].y);
+            w[3 * k + 2] = __float_as_uint(vs[k].z);
+        }
+        w[12] = scatter ? 1u : 0u;
+        w[13] = ps.seed;
+        return false;
+    }
     // shader.rgen:77-88
     V3 col, v = sd;
     bool more;
@@ -2339,6 +2358,46 @@ __global__ void rt_debug_math_kernel(int op, const float* __restrict__ in, float
     out[i] = r;
 }
 
+// Diagnostic (rt_debug_scatter, rt_probe_scatter.cpp): one bounce of K.n given hits, a lane per
+// case, by the frames' own shade_rec in its MODE_SCATTER instantiation: the STREAM path's shading of
+// a hit, which stores the bounce where a frame goes on to the next segment. Case i is ray i traced
+// along normalize(v), which hit sphere ids[i] at t[i] with the LCG in state seeds[i]. REC: the
+// sphere's records come from the static LDS table, staged as rt_trace_grid_kernel stages it
+// (load_hit_rec); otherwise from the scene's global arrays (load_hit). The host checked ids[i] <
+// n_spheres, and n_spheres <= kRecStatic for REC.
+template <bool REC>
+__global__ __launch_bounds__(256) void rt_scatter_probe_kernel(const rt::ScatterProbeParams K) {
+    const float4* mat4 = reinterpret_cast<const float4*>(K.mat);
+    if (REC) {
+        const uint32_t n = min(K.n_spheres, rt::kRecStatic);
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+            const rt::GeomRec g = K.geom[i];
+            s_rec[3 * i] = make_float4(g.cx, g.cy, g.cz, K.radius[i]);
+            s_rec[3 * i + 1] = mat4[2 * i];
+            s_rec[3 * i + 2] = mat4[2 * i + 1];
+        }
+        __syncthreads();
+    }
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K.n) return;
+    const float* q = K.rays + 6u * size_t(i);
+    V3 o = v3(q[0], q[1], q[2]);
+    V3 d = normalize(v3(q[3], q[4], q[5]));
+    const uint32_t bi = K.ids[i];
+    const HitRec hr = REC ? load_hit_rec(bi) : load_hit(reinterpret_cast<const float4*>(K.geom), mat4, bi);
+    // of the launch parameters MODE_SCATTER reads probe_out alone, and no camera (shade_rec says so at
+    // its MODE_SCATTER branch): the zeroed structs only fill its signature and compile away
+    rt::TraceParams P{};
+    P.probe_out = K.out;
+    const Camera cam{};
+    Path ps{};
+    ps.px = i;
+    ps.seed = K.seeds[i];
+    ps.thr = v3(1.0f, 1.0f, 1.0f);
+    bool fresh = false;
+    shade_rec<rt::MODE_SCATTER, false>(P, cam, hr, ps, bi, K.t[i], o, d, fresh);
+}
+
 // Diagnostic: rcp_cr / sqrt_cr against hipcc's correctly rounded 1.0f / x and sqrtf over all 2^32
 // inputs (base .. base + grid * 256); mismatches counted in bad[0] / bad[1] (NaN equals NaN). With
 // div_b != 0: the camera's float(double(x) * (1 / double(div_b))) against x / div_b for every
@@ -2521,6 +2580,14 @@ hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st) {
 
 hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st) {
     hipLaunchKernelGGL(rt_debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, st, op, in, out, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_scatter_probe(const ScatterProbeParams& K, bool rec, hipStream_t st) {
+    if (K.n == 0) return hipSuccess;
+    const dim3 grid((K.n + 255u) / 256u), block(256);
+    if (rec) hipLaunchKernelGGL(rt_scatter_probe_kernel<true>, grid, block, 0, st, K);
+    else hipLaunchKernelGGL(rt_scatter_probe_kernel<false>, grid, block, 0, st, K);
     return hipGetLastError();
 }
 

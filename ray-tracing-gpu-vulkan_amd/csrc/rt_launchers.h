@@ -8,7 +8,7 @@
 #include <stdint.h>
 
 namespace rt {
-struct TraceParams; struct Counters; struct TabSize;                      // rt_internal.h, rt_hand_out.h
+struct TraceParams; struct Counters; struct TabSize; struct ScatterProbeParams;   // rt_internal.h, rt_hand_out.h
 struct AdaptiveState; struct AdaptiveErrorParams; struct FeedbackParams;   // rt_adaptive.h
 namespace sample_map { struct DevicePlanParams; }                          // rt_sample_map_device.h
 
@@ -31,6 +31,7 @@ hipError_t launch_gather_rows(const float* src_acc, const uint32_t* rows, uint32
                               uint32_t src_rows, float* dst_acc, hipStream_t st);
 hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st);
 hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st);
+hipError_t launch_scatter_probe(const ScatterProbeParams& K, bool rec, hipStream_t st);
 // rt_adaptive.hip
 hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st);
 hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);

@@ -28,5 +28,22 @@ uint32_t stage_batch(const float* rays6, uint32_t n, std::vector<float>& rays, u
     return 0;
 }
 
+uint32_t check_scatter_batch(const float* rays6, const uint32_t* ids, const float* t, uint32_t n, uint32_t n_spheres) {
+    for (uint32_t i = 0; i < n; i++) {
+        const float* q = rays6 + 6u * size_t(i);
+        for (int k = 0; k < 6; k++)
+            if (!std::isfinite(q[k])) return i + 1u;
+        if (q[3] == 0.0f && q[4] == 0.0f && q[5] == 0.0f) return i + 1u;
+        if (!std::isfinite(t[i])) return i + 1u;
+        if (ids[i] >= n_spheres) return i + 1u;
+    }
+    return 0;
+}
+
+bool scatter_form_ok(uint32_t form, uint32_t n_spheres, uint32_t rec_capacity) {
+    if (form == kScatterFormGlobal) return true;
+    return form == kScatterFormRec && n_spheres <= rec_capacity;
+}
+
 }  // namespace probe
 }  // namespace rt

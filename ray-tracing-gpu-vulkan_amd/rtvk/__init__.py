@@ -284,6 +284,30 @@ class Renderer:
                                               ids.ctypes.data if n else None, t.ctypes.data if n else None))
         return ids, t
 
+    def scatter_probe(self, rays, ids, t, seeds, form: int = 0) -> dict:
+        """Diagnostic (rt_debug_scatter): one bounce of each of n given hits by the frames' shading
+        code. Case i: host ray rays[i] = (o, v), traced along the kernels' normalize(v), hit sphere
+        ids[i] at t[i] with the LCG in state seeds[i]. form 0 reads the sphere's records from the
+        scene's global arrays, 1 from the static LDS table of the grid kernels (at most 512
+        spheres). Returns {"p", "att", "sd" (the raw scatter direction), "d_next" (normalize of it,
+        zeros without a scatter): float32 [n, 3]; "scatter", "seed": uint32 [n]}. Synchronous."""
+        r = np.ascontiguousarray(rays, np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("rays must have shape [n, 6]")
+        n = r.shape[0]
+        k = np.ascontiguousarray(ids, np.uint32)
+        tt = np.ascontiguousarray(t, np.float32)
+        sd = np.ascontiguousarray(seeds, np.uint32)
+        if k.shape != (n,) or tt.shape != (n,) or sd.shape != (n,):
+            raise ValueError("ids, t and seeds must have shape [n]")
+        out = {name: np.zeros((n, 3), np.float32) for name in ("p", "att", "sd", "d_next")}
+        out["scatter"] = np.zeros(n, np.uint32)
+        out["seed"] = np.zeros(n, np.uint32)
+        ptr = (lambda a: a.ctypes.data) if n else (lambda a: None)
+        check(self._lib.rt_debug_scatter(self._ctx, ptr(r), ptr(k), ptr(tt), ptr(sd), n, form,
+                                         *(ptr(out[name]) for name in ("p", "att", "sd", "d_next", "scatter", "seed"))))
+        return out
+
     def render_device(self, rci: RenderCallInfo, accum, out, rows=None,
                       options: Optional[Options] = None, stream=None) -> None:
         """One band on this device, asynchronous on `stream` (torch current stream by default).

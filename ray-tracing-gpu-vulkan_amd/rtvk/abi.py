@@ -272,6 +272,7 @@ EXPORTS = {
     "rt_debug_tile_cost": (_I, [_P, _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_debug_scene": (_I, [_P, _U32, _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "rt_debug_closest_hits": (_I, [_P, _P, _U32, ctypes.POINTER(Options), _P, _P]),
+    "rt_debug_scatter": (_I, [_P, _P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P]),
     "ray_trace": (None, [_U32, ctypes.c_bool, _U32, _U32, _U32]),
     # include/rt_mi355x_debug.h (diagnostics, A/B, the multi-GPU frame plan)
     "rt_debug_multi_plan": (_I, [_U32, _U32, _U32, _P, _U32, _U32, _P, ctypes.c_uint64,

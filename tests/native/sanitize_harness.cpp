@@ -14,6 +14,7 @@
 //     frames; every group of every plan through the pairing the logical transport executes
 //     (pair_group), and mutilated groups refused;
 //   * the closest-hit probe's batch staging (csrc/rt_probe_batch.cpp) and the oracle's closest-hit entries;
+//   * the scatter probe's argument checks (the same file) and the oracle's orc_scatter;
 //   * the single-device launch plan and the row weights (csrc/rt_launch.cpp): scenes, bands, sample
 //     counts, streams, forms and tuning values of tests/test_launch_plan.py plus the extremes (one
 //     CU, 1x1 and 65535x65535 bands, 0 samples, no spheres, tuning values up to 2^32), every plan
@@ -49,6 +50,9 @@ int orc_closest_hits(const Sphere* spheres, uint32_t n, const float* rays6, uint
                      uint32_t* out_id, float* out_t, int threads);
 int orc_report_t(const Sphere* spheres, uint32_t n, const float* rays6, uint32_t n_rays, const uint32_t* ids,
                  float* out_t);
+int orc_scatter(const Sphere* spheres, uint32_t n, const float* rays6, const uint32_t* ids, const float* t,
+                const uint32_t* seeds, uint32_t n_cases, float* out_p, float* out_att, float* out_sd, float* out_dnext,
+                uint32_t* out_scatter, uint32_t* out_seed);
 int orc_render(const Sphere* spheres, uint32_t n, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_w,
                uint32_t band_h, const rt_options* opt, float* accum, uint8_t* out, uint64_t* stats3, int threads);
 int orc_resolve(const float* acc, uint64_t n_texels, uint32_t spp, uint8_t* out);
@@ -659,6 +663,57 @@ void check_probe_batch() {
     CHECK(orc_closest_hits(nullptr, 0, nullptr, 0, 1, nullptr, nullptr, 2) == 0);   // nothing to do
 }
 
+// The host half of rt_debug_scatter (csrc/rt_probe_batch.cpp check_scatter_batch, scatter_form_ok):
+// arrays of exactly n cases, every refusal at the first and at the last case, and the oracle's
+// orc_scatter on the same arrays with every material of the canonical scene.
+void check_scatter_batch() {
+    using rt::probe::check_scatter_batch;
+    using rt::probe::scatter_form_ok;
+    const std::vector<Sphere> s = scene(0.0f, 11);
+    const uint32_t ns = uint32_t(s.size());
+    for (uint32_t n : {1u, 63u, 257u, 1000u}) {
+        std::vector<float> rays(size_t(n) * 6u), t(n);
+        std::vector<uint32_t> ids(n), seeds(n);
+        for (uint32_t i = 0; i < n; i++) {
+            const float q[6] = {0.01f * float(i), 1.0f, -3.0f + 0.001f * float(i), 0.0f, -0.1f, 1.0f};
+            std::memcpy(&rays[6u * i], q, sizeof(q));
+            ids[i] = (i * 7u) % ns;
+            t[i] = 0.5f + 0.001f * float(i);
+            seeds[i] = 0x9e3779b9u * i;
+        }
+        CHECK(check_scatter_batch(rays.data(), ids.data(), t.data(), n, ns) == 0);
+        std::vector<float> p(size_t(n) * 3u), att(p.size()), sd(p.size()), dn(p.size());
+        std::vector<uint32_t> sc(n), after(n);
+        CHECK(orc_scatter(s.data(), ns, rays.data(), ids.data(), t.data(), seeds.data(), n, p.data(), att.data(), sd.data(),
+                          dn.data(), sc.data(), after.data()) == 0);
+        for (uint32_t i = 0; i < n; i++) CHECK(sc[i] <= 1u);
+        for (uint32_t at : {0u, n - 1u}) {
+            for (int k = 0; k < 6; k++) {
+                std::vector<float> bad = rays;
+                bad[6u * at + k] = k % 2 ? INFINITY : NAN;
+                CHECK(check_scatter_batch(bad.data(), ids.data(), t.data(), n, ns) == at + 1u);
+            }
+            std::vector<float> bad = rays;
+            bad[6u * at + 3] = 0.0f; bad[6u * at + 4] = -0.0f; bad[6u * at + 5] = 0.0f;
+            CHECK(check_scatter_batch(bad.data(), ids.data(), t.data(), n, ns) == at + 1u);
+            std::vector<float> bad_t = t;
+            bad_t[at] = at ? NAN : -INFINITY;
+            CHECK(check_scatter_batch(rays.data(), ids.data(), bad_t.data(), n, ns) == at + 1u);
+            std::vector<uint32_t> bad_id = ids;
+            bad_id[at] = at ? ns : 0xffffffffu;
+            CHECK(check_scatter_batch(rays.data(), bad_id.data(), t.data(), n, ns) == at + 1u);
+            CHECK(orc_scatter(s.data(), ns, rays.data(), bad_id.data(), t.data(), seeds.data(), n, p.data(), att.data(),
+                              sd.data(), dn.data(), sc.data(), after.data()) == -1);
+        }
+        CHECK(check_scatter_batch(rays.data(), ids.data(), t.data(), n, 0u) == 1u);   // an empty scene holds no id
+    }
+    CHECK(scatter_form_ok(0u, 0u, 512u) && scatter_form_ok(0u, 100000u, 512u));
+    CHECK(scatter_form_ok(1u, 512u, 512u) && !scatter_form_ok(1u, 513u, 512u));
+    CHECK(!scatter_form_ok(2u, 1u, 512u) && !scatter_form_ok(0xffffffffu, 1u, 512u));
+    CHECK(orc_scatter(nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr) == 0);   // nothing to do
+}
+
 }  // namespace
 
 int main() {
@@ -697,6 +752,7 @@ int main() {
     check_launch_plans();
     check_oracle();
     check_probe_batch();
+    check_scatter_batch();
     std::printf("sanitize harness: %d checks passed (ASan + UBSan)\n", g_checks);
     return 0;
 }

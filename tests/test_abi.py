@@ -111,6 +111,9 @@ def test_invalid_arguments(rtvk):
     # the closest-hit probe (rt_mi355x_debug.h): no context, before any device work
     assert lib.rt_debug_closest_hits(None, None, 0, None, None, None) == -1
     assert b"ctx" in lib.rt_last_error()
+    # the scatter probe: the same
+    assert lib.rt_debug_scatter(None, None, None, None, None, 0, 0, None, None, None, None, None, None) == -1
+    assert b"ctx" in lib.rt_last_error()
 
 
 def test_store_ppm(rtvk, tmp_path):

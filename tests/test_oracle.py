@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import closest_hit_cases as ch
+import scatter_cases as sc
 
 GOLDEN = Path(__file__).resolve().parent / "golden"
 
@@ -356,3 +357,178 @@ def test_closest_hits_match_render_hit_pattern(oracle):
     sky = np.all(acc[..., :3] == np.float32([0.7, 0.8, 1.0]), axis=-1).reshape(-1)
     np.testing.assert_array_equal(sky, ids == ch.MISS)
     assert 0.1 < sky.mean() < 0.9
+
+
+# ---- the shading checker (orc_scatter) against the float64 restatement of shader.rchit ----------
+
+@pytest.fixture(scope="module")
+def scatter_f64(oracle):
+    """Per scene: every family's cases, the oracle's bounce and float64's, computed once."""
+    memo = {}
+
+    def get(name):
+        if name not in memo:
+            scene, fams = sc.all_cases(oracle, name)
+            memo[name] = {fam: (args, oracle.scatter(scene, *args), sc.scatter_f64(scene, *args)) for fam, args in fams.items()}
+        return memo[name]
+    return get
+
+
+def _assert_kept(what, args, orc, f64, keep):
+    """The kept-case rules: does_scatter, the LCG state and the attenuation exactly, p and the raw
+    scatter direction within their tolerances. Returns the worst p and sd ratios (the measured C)."""
+    for name, ours, theirs in (("does_scatter", orc["scatter"].astype(bool), f64["scatter"]),
+                               ("seed_after", orc["seed"], f64["seed"]),
+                               ("attenuation", orc["att"].view(np.uint32), f64["att"].view(np.uint32))):
+        diff = ours != theirs
+        bad = np.flatnonzero(keep & (diff if diff.ndim == 1 else diff.any(axis=1)))
+        assert bad.size == 0, (what, name, [(int(i), args[0][i].tolist(), int(args[1][i]), float(args[2][i]), int(args[3][i]))
+                                            for i in bad[:3]])
+    # d_next is normalize of the oracle's own sd (in float64: within 2 ulps per coordinate), zeros without a scatter
+    sc_o = orc["scatter"].astype(bool)
+    own = sc.normalize(np.where(sc_o[:, None], orc["sd"].astype(np.float64), 1.0))
+    assert np.all(orc["d_next"][~sc_o] == 0.0)
+    assert np.abs(orc["d_next"] - own)[keep & sc_o].max(initial=0.0) <= 4.0 * sc.U, what
+    rp = np.abs(orc["p"] - f64["p"]).max(axis=1) / (sc.U * f64["p_scale"])
+    rs = np.abs(orc["sd"] - f64["sd"]).max(axis=1) / (sc.U * f64["sd_scale"])
+    cp, csd = (float(rp[keep].max()), float(rs[keep].max())) if keep.any() else (0.0, 0.0)
+    assert cp <= sc.C_P and csd <= sc.C_SD, (what, cp, csd)
+    return cp, csd
+
+
+@pytest.mark.parametrize("family", [f for f in sc.FAMILIES if f != "head_on"])
+@pytest.mark.parametrize("scene", sc.SCENES)
+def test_scatter_agrees_with_float64(scatter_f64, scene, family):
+    """closest_hit_shader and the kernels' shade_rec were written by the same hands from one reading
+    of shader.rchit, and are only ever compared with each other: the oracle's bounce against a
+    float64 restatement written from the GLSL. On the cases binary32 must decide as float64 does
+    (scatter_cases.kept: every margin above tau = 1e-4, 1 - cos^2 above 2^-20, and a metal's margin
+    above its resolution when reflect + fuzz ru is short) does_scatter, the LCG state afterwards and
+    the attenuation are equal, d_next is normalize of the oracle's own sd, p lies
+    within C_P 2^-24 (|o| + t) and the raw scatter direction within C_SD 2^-24 x its condition term;
+    the share left out is at most 1 % (generic, bounce) or 60 % (the threshold families)."""
+    args, orc, f64 = scatter_f64(scene)[family]
+    keep = sc.kept(f64)
+    excluded = 1.0 - keep.mean()
+    cp, csd = _assert_kept(f"{scene} {family}", args, orc, f64, keep)
+    by = {k: round(float(np.mean(v <= sc.TAU)), 4) for k, v in f64["margins"].items()}
+    short_w = int(((f64["margins"]["metal"] > sc.TAU) & (f64["margins"]["metal"] <= f64["metal_resolution"])).sum())
+    print(f"{scene} {family}: {len(keep)} cases, excluded {excluded:.4f} (below tau by margin {by}; {short_w} more cases by the "
+          f"metal resolution), worst p ratio {cp:.2f}, worst sd ratio {csd:.2f}")
+    assert excluded <= sc.EXCLUDED_MAX[family]
+    assert keep.sum() >= 4096
+
+
+@pytest.mark.parametrize("scene", sc.SCENES)
+def test_scatter_head_on(oracle, scatter_f64, scene):
+    """Rays aimed at a glass sphere's centre: cos_t = dot(-d, n) rounds above 1 in about one case of
+    six, 1 - cos^2 is negative, its sqrt NaN, `eta * NaN <= 1` false: the bounce reflects without a
+    draw, whatever the ior (1.0 included). That is shader.rchit:125-128 as written, so it is the
+    contract. Every case in which the oracle takes no draw has a float64 1 - cos^2 below 2^-20; every
+    other case obeys the kept-case rules."""
+    args, orc, f64 = scatter_f64(scene)["head_on"]
+    no_draw = orc["seed"] == args[3]
+    assert np.all(f64["mtype"] == 2)
+    assert np.all(f64["om"][no_draw] < sc.OM_MIN), float(f64["om"][no_draw].max())
+    keep = sc.kept(f64, head_on=True) & ~no_draw
+    cp, csd = _assert_kept(f"{scene} head_on", args, orc, f64, keep)
+    R = sc.records(sc.make_scene(oracle, scene))
+    share = {float(i): round(float(no_draw[R["attr"][args[1]] == np.float32(i)].mean()), 3) for i in sc.IORS}
+    print(f"{scene} head_on: no-draw share per ior {share}; {int(keep.sum())} of {int((~no_draw).sum())} drawing cases kept, "
+          f"worst p ratio {cp:.2f}, worst sd ratio {csd:.2f}")
+    assert no_draw.sum() >= 256 and keep.sum() >= 4096
+    # without a draw the bounce is the mirror's: straight back
+    np.testing.assert_array_equal(orc["scatter"][no_draw], 1)
+    d = sc.normalize(args[0][:, 3:].astype(np.float64))
+    assert np.abs(orc["sd"][no_draw] + d[no_draw]).max() < 1e-5
+
+
+def test_scatter_families_reach_their_edges(scatter_f64):
+    """What the families are for, on their own inputs, in float64: back faces and rays inside glass
+    (bounce), both sides of every threshold within TAU-decades of it (the threshold families), every
+    material, every draw count, absorbed and scattered bounces."""
+    for scene in sc.SCENES:
+        fams = scatter_f64(scene)
+        f = fams["generic"][2]
+        assert set(np.unique(f["mtype"])) == {0, 1, 2, 3, 7} and set(np.unique(f["draws"])) == {0, 1, 3}
+        assert (f["scatter"] == 0).sum() > 200
+        f = fams["bounce"][2]
+        back = ~f["front"] & (f["mtype"] <= 2)
+        assert back.sum() > 500 and (back & (f["mtype"] == 2)).sum() > 100      # back faces; from inside glass
+        args, _, f = fams["tir"]
+        near = f["margins"]["can_refract"] < 1e-2
+        assert (near & (f["draws"] == 0)).sum() > 2000 and (near & (f["draws"] == 1)).sum() > 2000
+        f = fams["metal_edge"][2]
+        near = f["margins"]["metal"] < 1e-2
+        assert (near & f["scatter"]).sum() > 2000 and (near & ~f["scatter"]).sum() > 2000
+        f = fams["diffuse_edge"][2]
+        assert np.all(np.sqrt((f["sd"] ** 2).sum(axis=1)) < 0.05)       # |n + ru| with dot(ru, n) < -0.999
+        f = fams["checker_edge"][2]
+        assert (f["margins"]["checker"] < 1e-2).mean() > 0.7
+        f = fams["grazing"][2]
+        assert (f["margins"]["face"] < 1e-2).mean() > 0.7
+
+
+def test_restatement_obeys_the_physics(oracle):
+    """The float64 restatement is pinned to the laws it restates, at 1e-12, so that it is not one
+    more private reading: the mirror law, Snell's law on the far side of the surface, unit length of
+    a refracted unit vector, Schlick's end points, ior 1 refracting straight on, diffuse output on
+    the normal's side, and the draw counts."""
+    rng = np.random.default_rng(5)
+    n = 4096
+    unit = lambda: sc.normalize(rng.normal(size=(n, 3)))
+    nrm, d = unit(), unit()
+    d = np.where((sc.dot(d, nrm) > 0)[:, None], -d, d)          # incoming: against the normal
+    # mirror law
+    r = sc.reflect(d, nrm)
+    assert np.abs(sc.dot(r, nrm) + sc.dot(d, nrm)).max() < 1e-12
+    assert np.abs(np.cross(r - d, nrm)).max() < 1e-12
+    # Snell, unit length, the far side
+    for eta in (1.0 / 1.5, 1.0 / 1.33, 1.5, 2.4, 1.0 / 0.6):
+        e = np.full(n, eta)
+        sin_i = np.linalg.norm(np.cross(d, nrm), axis=1)
+        ok = eta * sin_i < 1.0 - 1e-9
+        tr = sc.refract(d, nrm, e)
+        assert ok.sum() > 100
+        assert np.abs(np.linalg.norm(np.cross(tr, nrm), axis=1) - eta * sin_i)[ok].max() < 1e-12
+        assert np.abs(np.linalg.norm(tr, axis=1) - 1.0)[ok].max() < 1e-12
+        assert np.all(sc.dot(tr, nrm)[ok] < 0.0)
+        assert np.abs(np.cross(np.cross(d, nrm), np.cross(tr, nrm))).max() < 1e-12   # in the plane of incidence
+        assert np.all(tr[eta * sin_i > 1.0 + 1e-9] == 0.0)     # beyond the critical angle: GLSL's zero vector
+    assert np.abs(sc.refract(d, nrm, np.ones(n)) - d).max() < 1e-12
+    # Schlick
+    for eta in (0.6, 1.0 / 1.5, 1.0, 1.5, 2.4):
+        e = np.full(3, eta)
+        s = sc.schlick(np.array([1.0, 0.0, 0.5]), e)
+        r0 = ((1.0 - eta) / (1.0 + eta)) ** 2
+        assert abs(s[0] - r0) < 1e-12 and abs(s[1] - 1.0) < 1e-12 and r0 <= s[2] <= 1.0
+    # the whole bounce on a hand-made scene: one sphere of each material at the origin
+    base = oracle.generate_scene()[4:5]
+    for mtype, attr, draws in ((0, 0.0, 3), (1, 0.3, 3), (2, 1.5, 1), (2, 1.0, 1), (3, 0.0, 0), (7, 0.5, 0)):
+        rec = base.copy()
+        rec[0, :16].view(np.float32)[:] = [0.0, 0.0, 0.0, 1.0]
+        sc._write(rec[0], mtype, 0, (0.5, 0.6, 0.7), (0.1, 0.2, 0.3), attr)
+        o = (unit() * 3.0).astype(np.float32)
+        tgt = unit() * 0.7
+        rays = np.concatenate([o, (tgt - o).astype(np.float32)], axis=1).astype(np.float32)
+        dd = sc.normalize(rays[:, 3:].astype(np.float64))
+        b = sc.dot(o.astype(np.float64), dd)
+        t = (-b - np.sqrt(b * b - (sc.dot(o.astype(np.float64), o.astype(np.float64)) - 1.0))).astype(np.float32)
+        f = sc.scatter_f64(rec, rays, np.zeros(n, np.uint32), t, rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))
+        assert np.all(f["draws"] == draws), (mtype, attr)
+        nn = sc.normalize(f["p"])
+        if mtype == 0:
+            assert np.all(sc.dot(f["sd"], nn) >= 0.0)
+        if mtype >= 3:
+            assert not f["scatter"].any()
+        if mtype == 2 and attr == 1.0:
+            refr = np.abs(f["sd"] - dd).max(axis=1) < 1e-12
+            assert refr.mean() > 0.9 and np.abs(f["sd"][~refr] - sc.reflect(dd, nn)[~refr]).max() < 1e-12
+    # total internal reflection: inside glass beyond the critical angle there is no draw
+    rec = base.copy()
+    rec[0, :16].view(np.float32)[:] = [0.0, 0.0, 0.0, 1.0]
+    sc._write(rec[0], 2, 0, (1, 1, 1), (0, 0, 0), 1.5)
+    o = np.float32([[0.9, 0.0, 0.0]])
+    f = sc.scatter_f64(rec, np.concatenate([o, np.float32([[0.0, 1.0, 0.0]])], axis=1), np.zeros(1, np.uint32),
+                       np.float32([np.sqrt(1 - 0.81)]), np.uint32([7]))
+    assert f["draws"][0] == 0 and f["seed"][0] == 7 and f["scatter"][0]      # sin = 0.9 > 1 / 1.5
