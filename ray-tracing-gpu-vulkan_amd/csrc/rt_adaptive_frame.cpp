@@ -123,7 +123,7 @@ int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* r
     if (int rc = fill_trace(ctx, rci, rows, band_width, band_height, o, accum, out, st, f.S)) return rc;
     if (int rc = adaptive_reserve(ctx, uint64_t(band_width) * band_height, f.S.n_tiles, st)) return rc;
     rt::TraceParams& P = f.S.P;
-    // the walk kernels record tile costs unconditionally (rt_kernels.hip record_tile_cost): a
+    // the walk kernels record tile costs unconditionally (rt_trace_units.h record_tile_cost): a
     // scratch table of the whole tile grid, never read
     P.tile_cost = f.S.plan.accel != rt::ACCEL_BRUTE ? a.tiles + 3u * f.S.n_tiles : nullptr;
     P.accumulate = 0u;

@@ -4,7 +4,7 @@
 // launch_units), as the closest-hit probe is (rt_probe.cpp): one unit per pixel, so that one lane
 // sums a pixel's samples in ascending order. TraceParams::feat0 makes launch_trace pick the kernels'
 // MODE_FEATURES instantiation, which takes HASH's camera rays and ends each at its closest hit
-// (rt_kernels.hip shade_rec). The denoise is one kernel per iteration (rt_denoise.hip) by the launch
+// (rt_trace_shade.h shade_rec). The denoise is one kernel per iteration (rt_denoise.hip) by the launch
 // list of its HIP-free host half (rt_denoise_host.cpp); the variance-guided denoise likewise
 // (rt_denoise_var.hip, rt_denoise_var_host.cpp), on the same band planes of the context.
 #include <hip/hip_runtime.h>

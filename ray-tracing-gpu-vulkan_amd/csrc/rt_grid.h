@@ -1,6 +1,6 @@
 // rt_grid.h — uniform grid over the scene's small spheres (host build, rt_grid.cpp): the closest-hit
 // structure of the trace kernels for scenes of similar-size spheres, traversed by a 3D DDA
-// (rt_kernels.hip grid_walk). Replaces the driver BVH of src/vulkan.h:395-554 like the LBVH does.
+// (rt_trace_grid.h grid_walk). Replaces the driver BVH of src/vulkan.h:395-554 like the LBVH does.
 #pragma once
 
 #include <cmath>

@@ -1,6 +1,6 @@
 // rt_hand_out.h — the block hand-out of a trace launch as one rule for the host
 // plan (rt_launch.cpp hand_out_units) and for the device, which sizes a launch whose block table was
-// planned there (rt_kernels.hip rt_tab_size_kernel). No HIP, integers only.
+// planned there (rt_frame_kernels.hip rt_tab_size_kernel). No HIP, integers only.
 #pragma once
 
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // rt_internal.h — device data layout and launch parameters shared by the HIP kernels
-// (rt_kernels.hip) and the host runtime (rt_api.cpp and the frame kinds beside it, through
+// (rt_kernels.hip, its rt_trace_*.h headers and the units beside it) and the host runtime (rt_api.cpp and the frame kinds beside it, through
 // rt_context.h). Not part of the public C-ABI.
 #pragma once
 
@@ -91,7 +91,7 @@ struct GridInfo {
 #define RT_TRACE_BLOCK 768   // threads per block of the tree / grid kernels (rt_kernels.hip kTraceBlock)
 #endif
 // Static LDS of the grid kernels beside their dynamic LDS: per-thread 64-bit unit sums of the
-// counter-based stream (rt_kernels.hip s_lane_sum).
+// counter-based stream (rt_trace_units.h s_lane_sum).
 constexpr unsigned kLaneSumLdsBytes = 3u * 8u * RT_TRACE_BLOCK;
 // Wave-cooperative grid walk (ACCEL_GRID_COOP): per thread a ray (2 float4), a key (u64) and a
 // pass marker (u32) in LDS.
@@ -150,7 +150,7 @@ enum : uint32_t { ACCEL_BRUTE = 1, ACCEL_LBVH_GLOBAL = 2, ACCEL_LBVH_LDS = 3, AC
 //           order on one lane; each sample is HASH's camera ray, ended at its closest hit, whose
 //           albedo, normal and depth are summed in binary32 (TraceParams::feat0 / feat1).
 //   SCATTER: diagnostic (rt_debug_scatter): STREAM's shading of one given hit, whose bounce is stored
-//           where a frame goes on to its next segment (rt_kernels.hip rt_scatter_probe_kernel; never a
+//           where a frame goes on to its next segment (rt_debug_kernels.hip rt_scatter_probe_kernel; never a
 //           trace kernel's mode).
 enum : int { MODE_STREAM = 0, MODE_HASH = 1, MODE_PROBE = 2, MODE_FEATURES = 3, MODE_SCATTER = 4 };
 
@@ -181,7 +181,7 @@ struct Counters {
     unsigned long long stamp[8];   // diagnostic builds only (-DRT_STAMPS): cycles per phase
     unsigned long long util[2 * 16];   // diagnostic builds only (-DRT_UTIL): per code point k, wave
                                        // passes [2k] and active lanes summed over them [2k + 1]
-    unsigned long long steals;     // counter-based stream: tail steals (rt_kernels.hip steal_tail)
+    unsigned long long steals;     // counter-based stream: tail steals (rt_trace_units.h steal_tail)
     unsigned long long cells_empty;     // COUNT builds, grid walks: visited cells without references
     unsigned long long walk_split[4];   // COUNT builds: walk work (cells + references) per segment
                                         // pass, max over the wave's tracing lanes [0], over its bounce
@@ -213,7 +213,7 @@ struct TraceParams {
                                    // finite, so the ray origin lf + rx crt + ry cup (rx, ry = +-0, or
                                    // NaN when the disk sample is (0, 0)) is lf itself or NaN
     float size_x, size_y;          // full image size as float (shader.rgen:42)
-    double inv_size_x, inv_size_y; // 1 / size, rounded to double (camera division, rt_kernels.hip)
+    double inv_size_x, inv_size_y; // 1 / size, rounded to double (camera division, rt_trace_shade.h)
     uint32_t number, spp, max_depth;
     uint32_t seed_local;           // 1: seed from launch-local ids (shader.rgen:40 verbatim)
     uint32_t rng_counter;          // STREAM only, 1: RT_RNG_SAMPLE_COUNTER
@@ -284,7 +284,7 @@ struct TraceParams {
     float* feat1;                  // {sum n.xyz, sum depth}
 };
 
-// Parameters of the one-bounce diagnostic (rt_kernels.hip rt_scatter_probe_kernel, rt_probe_scatter.cpp).
+// Parameters of the one-bounce diagnostic (rt_debug_kernels.hip rt_scatter_probe_kernel, rt_probe_scatter.cpp).
 struct ScatterProbeParams {
     uint32_t n_spheres;
     const GeomRec* geom;
@@ -300,7 +300,7 @@ struct ScatterProbeParams {
 };
 
 // HASH mode fixed point: a sample colour channel c in [0, 1] (every colour and the sky are <= 1,
-// so is every product of them) adds trunc(c * 2^24) (rt_kernels.hip sample_fixed). A lane sums its
+// so is every product of them) adds trunc(c * 2^24) (rt_trace_units.h sample_fixed). A lane sums its
 // samples in 32 bits and adds the partial to the pixel's 64-bit sum whenever its next sample index
 // is a multiple of kFixedFlush, and at the end of its unit: a partial holds <= 128 * 2^24 = 2^31.
 constexpr int kFixedFracBits = 24;
@@ -309,7 +309,7 @@ constexpr uint32_t kFixedFlush = 128;
 // "Big" spheres (radius above a scene-relative threshold, e.g. the ground sphere) are tested by
 // every segment before the tree walk; at most kBigMax of them. A one-wave kernel writes their
 // records (center, radius) and ids into TraceParams::big_tab before each launch; the walk kernels
-// read them through the scalar cache (rt_kernels.hip setup_ray).
+// read them through the scalar cache (rt_trace_walk.h setup_ray).
 constexpr uint32_t kBigMax = 64;
 constexpr uint32_t kRecStatic = 512;   // spheres of the REC grid kernels' static LDS record table
 constexpr uint32_t kNoRowsLds = 0xffffffffu;

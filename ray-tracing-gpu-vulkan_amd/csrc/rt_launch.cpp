@@ -71,7 +71,7 @@ bool grid_walk(uint32_t accel) {
 
 void size_lds_forms(const Inputs& in, Plan& p) {
     const size_t tree = size_t(2 * in.n_nodes + in.n_leaf + (in.n_leaf + 3) / 4) * 16;
-    const size_t lds1 = tree;   // shading records stay in HBM (rt_kernels.hip)
+    const size_t lds1 = tree;   // shading records stay in HBM (rt_kernels.hip rt_trace_lds_kernel)
     const bool ok = in.n_nodes && in.n_leaf <= kMaxLdsLeafSlots && in.n_nodes <= kMaxLdsNodes;
     p.lds1_bytes = (ok && lds1 <= kMaxLdsBytes) ? lds1 : 0;
     const size_t oct = lds1 + size_t(14u) * in.n_nodes * 16u;
@@ -185,7 +185,7 @@ int plan_form(const Inputs& in, const Device& dev, Plan& p, const char** err) {
         }
     }
     // The row map of a banded launch (N > 1 strips) is staged in the walk kernels' dynamic LDS
-    // after their own data (band_row, rt_kernels.hip) when that keeps the blocks per CU; else it
+    // after their own data (band_row, rt_trace_units.h) when that keeps the blocks per CU; else it
     // is read from global memory.
     uint32_t rows_lds = rt::kNoRowsLds;
     const bool flat = dev.flat_grid_form(dev.user, in, accel, count);   // the kernel launch_trace picks

@@ -18,6 +18,7 @@ hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mo
 hipError_t trace_occupancy(uint32_t accel, bool count, int mode, bool flat, size_t lds_bytes, int* blocks_per_cu);
 bool flat_grid_form(const TraceParams& P, uint32_t accel, bool count);
 uint32_t block_size(uint32_t accel);
+// rt_frame_kernels.hip
 hipError_t launch_resolve_fixed(unsigned long long* fixed, uint64_t n_texels, uint32_t accumulate, uint32_t spp,
                                 float* accum, uint8_t* out, hipStream_t st);
 hipError_t launch_tonemap(const float* accum, uint64_t n_texels, uint32_t spp, uint8_t* out, hipStream_t st);
@@ -29,6 +30,7 @@ hipError_t launch_scatter_rows(const float* src_acc, const uint8_t* src_px, cons
                                hipStream_t st);
 hipError_t launch_gather_rows(const float* src_acc, const uint32_t* rows, uint32_t n_rows, uint32_t width,
                               uint32_t src_rows, float* dst_acc, hipStream_t st);
+// rt_debug_kernels.hip
 hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st);
 hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st);
 hipError_t launch_scatter_probe(const ScatterProbeParams& K, bool rec, hipStream_t st);

@@ -3,7 +3,7 @@
 // texel, planned and launched as a one-sample STREAM frame of that band through rt_api.cpp's own
 // steps (fill_trace, split_units, launch_units); TraceParams::probe_rays makes launch_trace pick the
 // kernels' MODE_PROBE instantiation, which loads a unit's ray where a frame computes the camera's
-// and stores (winner, t) where a frame shades (rt_kernels.hip start_sample, shade_rec). The host half
+// and stores (winner, t) where a frame shades (rt_trace_shade.h start_sample, shade_rec). The host half
 // (argument checks of the rays, the batch as a band) is rt_probe_batch.cpp, without HIP.
 #include <hip/hip_runtime.h>
 

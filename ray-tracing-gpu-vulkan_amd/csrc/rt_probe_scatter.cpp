@@ -1,5 +1,5 @@
 // rt_probe_scatter.cpp — rt_debug_scatter (include/rt_mi355x_debug.h): one bounce of a batch of given
-// hits by the frames' own shading (rt_kernels.hip shade_rec, instantiated as MODE_SCATTER: the STREAM
+// hits by the frames' own shading (rt_trace_shade.h shade_rec, instantiated as MODE_SCATTER: the STREAM
 // path's code for a hit, storing the bounce), a lane per case, with the sphere's records read the two ways the trace kernels read them:
 // from the scene's global arrays (load_hit) or from the static LDS table of the REC grid kernels
 // (load_hit_rec). No launch plan, no hand-out, no tile costs: the kernel is its own

@@ -1,6 +1,6 @@
 """Static ISA instruction counts per phase of one trace kernel (DESIGN.md §4.4's phase split).
 
-The kernels mark their phases with STAMP(k) (rt_kernels.hip); an -DRT_ASM_MARKS device-only
+The kernels mark their phases with STAMP(k) (rt_trace_diag.h); an -DRT_ASM_MARKS device-only
 listing turns each into an `; RT_PHASE k` comment where the phase begins in program order (0 loop
 head / refill, 4 sample start, 1 ray setup with the exhaustive big spheres, 2 walk, 3 shading,
 5 refill: block hand-out, 6 refill: block fetch). Instructions are attributed to the most recent

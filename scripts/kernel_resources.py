@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Per-kernel register / spill / occupancy table of a HIP source for gfx950 (compiler remarks).
+"""Per-kernel register / spill / occupancy table of HIP sources for gfx950 (compiler remarks).
 
-usage: python scripts/kernel_resources.py [file.hip] [extra hipcc flags...]
+usage: python scripts/kernel_resources.py [file.hip ...] [extra hipcc flags...]
+Without a file: the device units that hold the trace kernels and the resolve kernel.
 """
 import re
 import subprocess
@@ -9,11 +10,13 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
-src = sys.argv[1] if len(sys.argv) > 1 else str(ROOT / "ray-tracing-gpu-vulkan_amd/csrc/rt_kernels.hip")
+CSRC = ROOT / "ray-tracing-gpu-vulkan_amd/csrc"
+srcs = [a for a in sys.argv[1:] if a.endswith(".hip")] or [str(CSRC / "rt_kernels.hip"), str(CSRC / "rt_frame_kernels.hip")]
+flags = [a for a in sys.argv[1:] if not a.endswith(".hip")]
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
        f"-I{ROOT / 'include'}", "--offload-arch=gfx950", "-fno-gpu-rdc", "-fno-slp-vectorize",
-       "--cuda-device-only", "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + sys.argv[2:]
-err = subprocess.run(cmd, capture_output=True, text=True).stderr
+       "--cuda-device-only", "-c", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + flags
+err = "".join(subprocess.run(cmd + [src], capture_output=True, text=True).stderr for src in srcs)
 rows, cur = [], None
 for line in err.splitlines():
     m = re.search(r"Function Name: (\S+)", line)

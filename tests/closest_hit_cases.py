@@ -142,7 +142,7 @@ _TINY = np.array([0.0, -0.0, 1e-42, -1e-42, 4e-39, -4e-39, 1e-36, -1e-36, 1e-32,
 
 # The ray the probe caught on `cloud` (every LBVH form missed sphere 22, t = 0.028013617): the y
 # component of its direction normalises to a denormal, 1 / d.y = 2.3e38 is finite, and the node
-# test's o.y / d.y overflowed (rt_kernels.hip node_inv clamped the infinite reciprocal only).
+# test's o.y / d.y overflowed (rt_trace_walk.h node_inv clamped the infinite reciprocal only).
 DENORMAL_RAY = np.array([3191271496, 1075883891, 3217741472, 2147483648, 714, 3111091543], np.uint32).view(np.float32)
 
 

@@ -496,7 +496,7 @@ def test_hash_head_tail_chunks(rtvk, renderer, torch, oracle, head, tail_pm):
 
 
 def test_hash_tail_steals(rtvk, renderer, torch, oracle):
-    """Tail stealing (rt_kernels.hip steal_tail): one chunk per pixel and fewer units than lanes,
+    """Tail stealing (rt_trace_units.h steal_tail): one chunk per pixel and fewer units than lanes,
     so the queue is empty at once and lanes whose pixels end early (sky) take halves of the
     samples their wave's busiest lanes have not started. The frame keeps the oracle's bits and
     counts for the grid and brute-force kernels (the instrumented builds count the steals; the
