@@ -564,6 +564,81 @@ int rt_denoise_variance_device(rt_context* ctx, const float* accum_a, const floa
                                const float* feat1, uint32_t feature_samples, uint32_t band_width,
                                uint32_t band_height, const rt_denoise_variance* params,
                                float* out_mean_rgba32f, uint8_t* out_rgba8, void* stream);
+/*
+ * Temporal accumulation: a stage between the render and the two filters above
+ * for frame loops. A state object keeps, per texel of its band, the demodulated colour integrated
+ * over the frames before, the number of frames it holds and the first-hit guide of the last frame;
+ * one call blends the current frame into it wherever the guide still matches and starts over where
+ * it does not, and writes accumulators the filters read as they read a frame's. The state of a band
+ * of W x H texels is three float4 planes owned by the object:
+ *     HA = (eA.rgb, n)    HB = (eB.rgb, n)    HG = (nrm.xyz, z)
+ * n, the history length, is held as a float (exact up to 65 535) and is 0 after create and after
+ * reset. Every operation is one correctly rounded binary32 + - x /, in this order
+ * (tests/temporal_sim.py gives the same bits); no neighbour is read, the update is in place:
+ *     h   = sample_count ? sample_count[p] : spp;   hf = float(h)
+ *     cA  = h ? A.rgb / hf : 0                          (cB likewise when accum_b is given)
+ *     a   = feat0.rgb / float(F) + 2^-6;  nrm = feat1.xyz / float(F);  z = feat1.w / float(F)
+ *     eA  = cA / a                                                           (per channel)
+ *     dn  = nrm - HG.xyz;  dn2 = (dn.x dn.x + dn.y dn.y) + dn.z dn.z
+ *     dz  = (z - HG.w) / (z + 1)
+ *     x   = (1 + k_normal dn2) (1 + k_depth (dz dz))
+ *     valid = HA.w > 0 and x < 2
+ *     h == 0 (no measurement this frame):
+ *         valid ? (e' = the history, n' = HA.w) : (e' = 0, n' = 0)
+ *     h > 0:
+ *         n' = valid ? min(HA.w + 1, float(max_history)) : 1;   alpha = 1 / n'
+ *         eA' = valid ? HA.rgb + alpha (eA - HA.rgb) : eA     (eB' with HB, the same valid and alpha)
+ *     HA = (eA', n');  HB = (eB', n');  HG = (nrm, z)          (the guide is always the current one)
+ *     out_a = (eA' a, 1);  out_b = (eB' a, 1)
+ *     out_rgba8 = rt_resolve_rgba8 at spp 1 of the mean: ((eA' + eB') * 0.5) a with two accumulators,
+ *                 eA' a with one
+ *     history_len[p] = uint32(n')
+ * Feeding the filters: out_a alone is an accumulator at 1 sample, which rt_denoise_device takes with
+ * spp = 1; out_a and out_b are two halves at half_spp = 1 for rt_denoise_variance_device. Both halves
+ * are integrated with the same weights, so they stay independent estimates of equal weight and
+ * |A - B|^2 / 4 stays a variance estimate of their mean.
+ * Sample ranges: the caller renders every frame from a disjoint sample range (sample_base += spp per
+ * frame; under two halves, the halves of frame k at k spp and k spp + spp / 2), or the frames repeat
+ * one another's noise and integrating them gains nothing. The features are rendered at the SAME
+ * sample_base every frame: a static scene then gives bit-identical guides, x = 1 exactly, and every
+ * texel is valid.
+ *   accum_a, accum_b  DEVICE float4 arrays of the state's band, summed accumulators of h_p samples
+ *                     each; accum_b optional: NULL is one accumulator, HB is then neither read nor
+ *                     written and out_b must be NULL too (and the reverse).
+ *   sample_count      optional DEVICE array of uint32 per texel; NULL: every texel has `spp` samples.
+ *   feat0, feat1, feature_samples   as rt_render_features_device wrote them.
+ *   params            NULL: {8, 4.0f, 16.0f, 0}.
+ *   out_a, out_b      DEVICE float4 arrays; out_rgba8 (4 bytes per texel) and history_len (uint32 per
+ *                     texel): optional.
+ * The call has no band-size arguments: the band is the state's own, and every array holds that many
+ * texels. One kernel launch on `stream`, nothing waits on the host and nothing is allocated: the
+ * planes are allocated by rt_temporal_create. RT_ERR_INVALID_ARGUMENT before anything is queued, with
+ * rt_last_error() naming the field: rt_denoise_check's size and feature-sample limits, max_history
+ * outside 2 .. 65535, a k that is negative or not finite, reserved not 0, a state of another context,
+ * out_b without accum_b or the reverse, a required pointer that is NULL. A state belongs to the
+ * context it was created on and must be destroyed before it, as a sample map. rt_temporal_reset sets
+ * n = 0 everywhere, queued on `stream` without a host wait: the next call is a first frame.
+ * rt_temporal_check is the parameter check alone (host only, no device).
+ * Not part of the stage: weighting frames by their sample counts, reprojection under camera or
+ * object motion (a texel whose surface changed starts over), sharing the pass with the filters'
+ * prologue.
+ */
+typedef struct rt_temporal rt_temporal;
+typedef struct rt_temporal_params {
+    uint32_t max_history;     /* 2 .. 65535: the blend weight never falls below 1 / max_history */
+    float k_normal, k_depth;  /* finite, >= 0 */
+    uint32_t reserved;        /* 0 */
+} rt_temporal_params;
+int rt_temporal_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_temporal** out);
+int rt_temporal_destroy(rt_temporal* temporal);
+int rt_temporal_reset(rt_temporal* temporal, void* stream);
+int rt_temporal_check(const rt_temporal_params* params, uint32_t band_width, uint32_t band_height,
+                      uint32_t feature_samples);
+int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a, const float* accum_b,
+                                  const uint32_t* sample_count, uint32_t spp, const float* feat0,
+                                  const float* feat1, uint32_t feature_samples, const rt_temporal_params* params,
+                                  float* out_a, float* out_b, uint8_t* out_rgba8, uint32_t* history_len,
+                                  void* stream);
 
 /* ---- multi-device (one process, N GPUs, RCCL over xGMI) ----------------------------- */
 typedef struct rt_multi rt_multi;

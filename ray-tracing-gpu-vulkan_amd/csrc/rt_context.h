@@ -215,6 +215,15 @@ struct rt_sample_map {
     unsigned long long* moved = nullptr;
 };
 
+// The state of a temporal stage (rt_temporal_create): three float4 planes of the
+// band in one allocation, HA, HB and HG (rt_temporal_host.h), written only by the work that
+// rt_temporal_accumulate_device and rt_temporal_reset queue.
+struct rt_temporal {
+    rt_context* ctx = nullptr;
+    uint32_t band_w = 0, band_h = 0;
+    float* planes = nullptr;
+};
+
 namespace rt {
 
 // Stream chaining of a context's device operations (rt_context::ev_last): order_on before an op on

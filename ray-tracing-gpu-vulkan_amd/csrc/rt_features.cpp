@@ -6,10 +6,13 @@
 // MODE_FEATURES instantiation, which takes HASH's camera rays and ends each at its closest hit
 // (rt_trace_shade.h shade_rec). The denoise is one kernel per iteration (rt_denoise.hip) by the launch
 // list of its HIP-free host half (rt_denoise_host.cpp); the variance-guided denoise likewise
-// (rt_denoise_var.hip, rt_denoise_var_host.cpp), on the same band planes of the context.
+// (rt_denoise_var.hip, rt_denoise_var_host.cpp), on the same band planes of the context. The temporal
+// stage in front of them is a state object of its own and one kernel (rt_temporal.hip) by the checks
+// of its host half (rt_temporal_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 #include <string>
 
 #include "../../include/rt_mi355x_debug.h"
@@ -19,6 +22,8 @@
 #include "rt_denoise_var.h"
 #include "rt_denoise_var_host.h"
 #include "rt_launchers.h"
+#include "rt_temporal.h"
+#include "rt_temporal_host.h"
 
 using rt::fail;
 
@@ -211,5 +216,104 @@ extern "C" int rt_denoise_variance_device(rt_context* ctx, const float* accum_a,
         }
         RT_HIP(rt::launch_denoise_var(K, L.prefilter != 0u, first, last, L.lds_step, st));
     }
+    return rt::mark_issued(ctx, st);
+}
+
+extern "C" int rt_temporal_check(const rt_temporal_params* params, uint32_t band_width, uint32_t band_height,
+                                 uint32_t feature_samples) {
+    rt_temporal_params p;
+    const char* err = "";
+    if (int rc = rt::temporal::check(params, band_width, band_height, feature_samples, &p, &err)) return fail(rc, err);
+    return RT_OK;
+}
+
+extern "C" int rt_temporal_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_temporal** out) {
+    if (!ctx || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_create: ctx or out is NULL");
+    *out = nullptr;
+    const char* err = "";
+    if (int rc = rt::temporal::check_band(band_width, band_height, &err)) return fail(rc, err);
+    rt::DeviceGuard g(ctx->device);
+    rt_temporal* t = new (std::nothrow) rt_temporal;
+    if (!t) return fail(RT_ERR_OUT_OF_MEMORY, "rt_temporal_create: out of host memory");
+    t->ctx = ctx;
+    t->band_w = band_width;
+    t->band_h = band_height;
+    const size_t bytes = size_t(rt::temporal::state_bytes(band_width, band_height));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->planes), bytes);
+    // n = 0 everywhere before the call returns: the first accumulate may come on any stream
+    if (e == hipSuccess) e = hipMemsetAsync(t->planes, 0, bytes, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        (void)hipFree(t->planes);
+        delete t;
+        return rt::fail_hip(e, "rt_temporal_create");
+    }
+    *out = t;
+    return RT_OK;
+}
+
+extern "C" int rt_temporal_destroy(rt_temporal* temporal) {
+    if (!temporal) return RT_OK;
+    rt::DeviceGuard g(temporal->ctx->device);
+    (void)hipFree(temporal->planes);   // waits for the queued calls that still use the planes
+    delete temporal;
+    return RT_OK;
+}
+
+extern "C" int rt_temporal_reset(rt_temporal* temporal, void* stream) {
+    if (!temporal) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_reset: temporal is NULL");
+    rt_context* ctx = temporal->ctx;
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    RT_HIP(hipMemsetAsync(temporal->planes, 0, size_t(rt::temporal::state_bytes(temporal->band_w, temporal->band_h)), st));
+    return rt::mark_issued(ctx, st);
+}
+
+extern "C" int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a,
+                                             const float* accum_b, const uint32_t* sample_count, uint32_t spp,
+                                             const float* feat0, const float* feat1, uint32_t feature_samples,
+                                             const rt_temporal_params* params, float* out_a, float* out_b,
+                                             uint8_t* out_rgba8, uint32_t* history_len, void* stream) {
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: ctx is NULL");
+    if (!temporal) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: temporal is NULL");
+    if (temporal->ctx != ctx)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: temporal belongs to another context");
+    rt_temporal_params p;
+    const char* err = "";
+    if (int rc = rt::temporal::check(params, temporal->band_w, temporal->band_h, feature_samples, &p, &err))
+        return fail(rc, err);
+    if (!accum_a || !feat0 || !feat1 || !out_a)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: accum_a, feat0, feat1 or out_a is NULL");
+    if (accum_b && !out_b)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: accum_b is given and out_b is NULL");
+    if (out_b && !accum_b)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: out_b is given and accum_b is NULL");
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    const uint64_t plane = rt::temporal::plane_floats(temporal->band_w, temporal->band_h);
+    rt::TemporalParams K;
+    std::memset(&K, 0, sizeof(K));
+    K.band_w = temporal->band_w;
+    K.band_h = temporal->band_h;
+    K.spp = spp;
+    K.feature_samples = float(feature_samples);
+    K.k_normal = p.k_normal;
+    K.k_depth = p.k_depth;
+    K.max_history = float(p.max_history);
+    K.accum_a = accum_a;
+    K.accum_b = accum_b;
+    K.sample_count = sample_count;
+    K.feat0 = feat0;
+    K.feat1 = feat1;
+    K.ha = temporal->planes;
+    K.hb = temporal->planes + plane;
+    K.hg = temporal->planes + 2u * plane;
+    K.out_a = out_a;
+    K.out_b = out_b;
+    K.out_rgba8 = reinterpret_cast<uint32_t*>(out_rgba8);
+    K.history_len = history_len;
+    RT_HIP(rt::launch_temporal(K, st));
     return rt::mark_issued(ctx, st);
 }

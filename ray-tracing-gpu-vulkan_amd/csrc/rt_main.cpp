@@ -28,13 +28,21 @@
 //   --adaptive frame), then first-hit feature buffers of F samples per pixel (default 16,
 //   rt_render_features_device) and the edge-avoiding denoise of ITER iterations (default 3,
 //   rt_denoise_device); --store writes the denoised image. Refused with --gpus above 1, with
-//   --frames, and on the plain path without --rng hash.
+//   --frames (but for --temporal below), and on the plain path without --rng hash.
 //   --denoise-variance [F[,ITER[,PRE]]]: one frame on one GPU in the counter-based stream (--rng
 //   hash) rendered as two halves of --samples / 2 (rt_render_device at sample_base 0 and
 //   --samples / 2), then the feature buffers of F samples and the variance-guided denoise of PRE
 //   prefilter passes (default 2) and ITER iterations (default 3, rt_denoise_variance_device);
 //   --store writes the denoised image. Takes --denoise's refusals, and refuses an odd --samples,
 //   --adaptive, and --denoise beside it.
+//   --temporal [N]: beside --denoise or --denoise-variance and --frames K [--animate], the one pairing
+//   of a filter with the frame loop: frame k is rendered at sample_base k x --samples (under
+//   --denoise-variance as two halves at k x --samples and k x --samples + --samples / 2), the
+//   features at sample_base 0, and the frame is integrated into a per-pixel history of at most N
+//   frames (default 8, rt_temporal_accumulate_device) that the filter then reads, everything queued
+//   on one stream; prints duration_per_frame; --store writes the last frame's filtered image. Refused
+//   without a filter, without --frames, with --gpus above 1, with --adaptive, without --rng hash, and
+//   when K x --samples does not fit 32 bits.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -410,6 +418,112 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     return 0;
 }
 
+// The denoised frame loop on device 0 (--temporal with --frames and a filter): frame k renders the
+// scene at t from the sample range of its own (sample_base = k x samples; under the variance filter
+// as two halves at k x samples and k x samples + samples / 2), the features at sample_base 0 every
+// frame, integrates the frame into the temporal state and filters what that call wrote, everything
+// queued on one stream. dv: the variance-guided filter's parameters, or nullptr for the plain
+// filter's dn. The stored image is the last frame's filtered one.
+int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate, bool store,
+                        uint32_t feature_samples, const rt_denoise& dn, const rt_denoise_variance* dv,
+                        const rt_temporal_params& tp) {
+    rt_context* ctx = nullptr;
+    rt_temporal* temporal = nullptr;
+    hipStream_t stream = nullptr;
+    float *accum_a = nullptr, *accum_b = nullptr, *feat0 = nullptr, *feat1 = nullptr, *out_a = nullptr, *out_b = nullptr;
+    uint8_t* rgba8 = nullptr;
+    const size_t texels = size_t(width) * height;
+    const uint32_t half = samples / 2u;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_RT(rt_temporal_create(ctx, width, height, &temporal));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    CLI_HIP(hipMalloc(&accum_a, texels * 16));
+    CLI_HIP(hipMalloc(&out_a, texels * 16));
+    if (dv) {
+        CLI_HIP(hipMalloc(&accum_b, texels * 16));
+        CLI_HIP(hipMalloc(&out_b, texels * 16));
+    }
+    CLI_HIP(hipMalloc(&feat0, texels * 16));
+    CLI_HIP(hipMalloc(&feat1, texels * 16));
+    CLI_HIP(hipMalloc(&rgba8, texels * 4));
+    rt_options feat_opt;
+    std::memset(&feat_opt, 0, sizeof(feat_opt));
+    feat_opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0;
+    uint32_t frame_index = 0;
+    const auto t_start = std::chrono::steady_clock::now();
+    auto frame = [&]() -> int {
+        const float t = animate ? std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() : 0.0f;
+        CLI_RT(rt_generate_scene(t, 11, scene.data(), uint32_t(scene.size()), &cnt));
+        CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+        RenderCallInfo rci;
+        CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+        rt_options opt = feat_opt;
+        opt.sample_base = frame_index * samples;
+        if (dv) {
+            RenderCallInfo half_rci = rci;
+            half_rci.samplesPerRenderCall = half;
+            rt_options second = opt;
+            second.sample_base = opt.sample_base + half;
+            CLI_RT(rt_render_device(ctx, &half_rci, nullptr, width, height, accum_a, rgba8, &opt, stream));
+            CLI_RT(rt_render_device(ctx, &half_rci, nullptr, width, height, accum_b, rgba8, &second, stream));
+        } else {
+            CLI_RT(rt_render_device(ctx, &rci, nullptr, width, height, accum_a, rgba8, &opt, stream));
+        }
+        CLI_RT(rt_render_features_device(ctx, &rci, nullptr, width, height, feat0, feat1, feature_samples, &feat_opt, stream));
+        CLI_RT(rt_temporal_accumulate_device(ctx, temporal, accum_a, accum_b, nullptr, dv ? half : samples, feat0, feat1,
+                                             feature_samples, &tp, out_a, out_b, nullptr, nullptr, stream));
+        if (dv)
+            CLI_RT(rt_denoise_variance_device(ctx, out_a, out_b, nullptr, 1, feat0, feat1, feature_samples, width, height, dv,
+                                              nullptr, rgba8, stream));
+        else
+            CLI_RT(rt_denoise_device(ctx, out_a, nullptr, 1, feat0, feat1, feature_samples, width, height, &dn, nullptr, rgba8,
+                                     stream));
+        ++frame_index;
+        return 0;
+    };
+    if (int rc = frame()) return rc;   // warm-up: the context's band buffers exist
+    CLI_RT(rt_temporal_reset(temporal, stream));
+    CLI_HIP(hipStreamSynchronize(stream));
+    frame_index = 0;
+    uint32_t done = 0;
+    while (done < frames) {
+        const auto b = std::chrono::steady_clock::now();
+        uint32_t k = 0;
+        for (;;) {
+            if (int rc = frame()) return rc;
+            ++k;
+            if (done + k >= frames) break;
+            if (std::chrono::steady_clock::now() - b > std::chrono::milliseconds(1000)) break;
+        }
+        CLI_HIP(hipStreamSynchronize(stream));
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+        done += k;
+        std::printf("duration_per_frame: %.3f ms (%u frames, %u spp%s, temporal history %u, %s denoise: %u feature samples, "
+                    "%.1f Msamples/s)\n",
+                    sec / k * 1e3, k, samples, dv ? " in two halves" : "", tp.max_history, dv ? "variance-guided" : "plain",
+                    feature_samples, double(width) * height * samples * k / sec / 1e6);
+    }
+    if (store) {   // the last frame
+        std::vector<uint8_t> img(texels * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_temporal_destroy(temporal);
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    (void)hipFree(accum_a);
+    (void)hipFree(accum_b);
+    (void)hipFree(out_a);
+    (void)hipFree(out_b);
+    (void)hipFree(feat0);
+    (void)hipFree(feat1);
+    (void)hipFree(rgba8);
+    return 0;
+}
+
 // F[,ITER]
 bool parse_denoise(const char* s, uint32_t& f, uint32_t& iter) {
     const std::string v = s;
@@ -459,6 +573,8 @@ int main(int argc, const char** argv) {
     bool denoise_variance = false;
     uint32_t dv_feature_samples = 16;
     rt_denoise_variance dv = {3u, 2u, 4.0f, 16.0f, 0.25f};
+    bool temporal = false;
+    rt_temporal_params tp = {8u, 4.0f, 16.0f, 0u};
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
@@ -488,6 +604,9 @@ int main(int argc, const char** argv) {
             std::puts("--denoise-variance [<F>[,<iter>[,<pre>]]]  # One GPU, hash stream, one frame of an even sample count as");
             std::puts("                                  # two halves, features of F samples, then the variance-guided filter:");
             std::puts("                                  # pre prefilter passes (default 2), iter iterations (default 3)");
+            std::puts("--temporal [<N>]                  # With --frames and --denoise or --denoise-variance: every frame takes");
+            std::puts("                                  # a sample range of its own and is integrated into a per-pixel");
+            std::puts("                                  # history of at most N frames (default 8) ahead of the filter");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -510,6 +629,15 @@ int main(int argc, const char** argv) {
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // the optional value
                 if (!parse_denoise_variance(argv[i + 1], dv_feature_samples, dv.iterations, dv.prefilter)) {
                     std::fprintf(stderr, "--denoise-variance takes F[,ITER[,PRE]]\n");
+                    return 2;
+                }
+                ++i;
+            }
+        } else if (a == "--temporal") {
+            temporal = true;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') {   // the optional value
+                if (!parse_u32(argv[i + 1], tp.max_history)) {
+                    std::fprintf(stderr, "--temporal takes N\n");
                     return 2;
                 }
                 ++i;
@@ -578,6 +706,37 @@ int main(int argc, const char** argv) {
             return 2;
         }
     }
+    if (temporal) {   // refused before anything renders
+        if (!denoise && !denoise_variance) {
+            std::fprintf(stderr, "--temporal feeds a filter: it needs --denoise or --denoise-variance\n");
+            return 2;
+        }
+        if (frames == 0) {
+            std::fprintf(stderr, "--temporal integrates the frames of a loop: it needs --frames\n");
+            return 2;
+        }
+        if (gpu_count > 1) {
+            std::fprintf(stderr, "--temporal runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
+            return 2;
+        }
+        if (adaptive) {
+            std::fprintf(stderr, "--temporal renders plain frames: it cannot run with --adaptive\n");
+            return 2;
+        }
+        if (!(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
+            std::fprintf(stderr, "--temporal needs the counter-based stream: give --rng hash\n");
+            return 2;
+        }
+        if (uint64_t(frames) * samples > 0xffffffffull) {
+            std::fprintf(stderr, "--temporal gives every frame a sample range of its own: --frames %u x --samples %u exceeds 32 bits\n",
+                         frames, samples);
+            return 2;
+        }
+        if (rt_temporal_check(&tp, width, height, denoise_variance ? dv_feature_samples : feature_samples) != RT_OK) {
+            std::fprintf(stderr, "--temporal: %s\n", rt_last_error());
+            return 2;
+        }
+    }
     if (denoise_variance) {   // refused before anything renders
         if (denoise) {
             std::fprintf(stderr, "--denoise-variance is a filter of its own: it cannot run with --denoise\n");
@@ -591,7 +750,7 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--denoise-variance runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
-        if (frames > 0) {
+        if (frames > 0 && !temporal) {
             std::fprintf(stderr, "--denoise-variance renders one frame: it cannot run with --frames\n");
             return 2;
         }
@@ -613,7 +772,7 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--denoise runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
-        if (frames > 0) {
+        if (frames > 0 && !temporal) {
             std::fprintf(stderr, "--denoise renders one frame: it cannot run with --frames\n");
             return 2;
         }
@@ -631,6 +790,12 @@ int main(int argc, const char** argv) {
     if (rt_device_count(&n) != RT_OK) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
+    }
+    if (temporal) {
+        const rt_denoise dn = {denoise_iterations, 4.0f, 16.0f, 1.0f};
+        return run_temporal_frames(samples, width, height, frames, animate, store,
+                                   denoise_variance ? dv_feature_samples : feature_samples, dn,
+                                   denoise_variance ? &dv : nullptr, tp);
     }
     if (denoise_variance) return run_denoised_variance(samples, width, height, store, dv_feature_samples, dv);
     if (denoise) return run_denoised(samples, width, height, store, adaptive ? &ad : nullptr, feature_samples, denoise_iterations);

@@ -32,6 +32,7 @@ __all__ = [
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
     "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
     "make_denoise", "denoise_check", "make_denoise_variance", "denoise_variance_check",
+    "Temporal", "make_temporal", "temporal_check",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -126,6 +127,23 @@ def denoise_variance_check(params: Optional["abi.DenoiseVariance"], band_w: int,
     refuse."""
     check(load_library().rt_denoise_variance_check(ctypes.byref(params) if params is not None else None,
                                                    band_w, band_h, feature_samples))
+
+
+def make_temporal(max_history: int = 8, k_normal: float = 4.0, k_depth: float = 16.0) -> "abi.TemporalParams":
+    """rt_temporal_params of Renderer.temporal_accumulate: a texel's history holds at most
+    `max_history` frames (2..65535; the blend weight of a frame never falls below 1 / max_history),
+    and it starts over where the first-hit normal or the relative first-hit depth moved, by the
+    filters' feature stop with these strengths (finite, >= 0). The defaults are the library's."""
+    t = abi.TemporalParams()
+    t.max_history, t.k_normal, t.k_depth, t.reserved = max_history, k_normal, k_depth, 0
+    return t
+
+
+def temporal_check(params: Optional["abi.TemporalParams"], band_w: int, band_h: int, feature_samples: int) -> None:
+    """rt_temporal_check (host only): raises RtError where Renderer.temporal_accumulate would
+    refuse its parameters."""
+    check(load_library().rt_temporal_check(ctypes.byref(params) if params is not None else None,
+                                           band_w, band_h, feature_samples))
 
 
 def threshold_q16(threshold: float) -> int:
@@ -509,6 +527,54 @@ class Renderer:
                                                    ctypes.byref(params) if params is not None else None,
                                                    mean_ptr, out.data_ptr(), _stream_ptr(stream, self.device)))
 
+    def temporal(self, width: int, height: int) -> "Temporal":
+        """The state of a temporal stage for a band of width x height texels on this context
+        (rt_temporal_create): every texel's history is empty. Close it before the renderer."""
+        t = Temporal(self, width, height)
+        self._maps.add(t)   # closed with the renderer at the latest
+        return t
+
+    def temporal_accumulate(self, temporal: "Temporal", accum_a, feat0, feat1, feature_samples: int, out_a,
+                            accum_b=None, out_b=None, out_rgba8=None, history_len=None, spp: Optional[int] = None,
+                            sample_count=None, params: Optional["abi.TemporalParams"] = None, stream=None) -> None:
+        """One frame into `temporal`'s history (rt_temporal_accumulate_device): accum_a (and accum_b,
+        a frame rendered as two halves) are summed accumulators of the temporal's band, each texel
+        holding `spp` samples or those of the 4-byte integer cuda tensor sample_count [band_h, band_w]
+        (exactly one of them); feat0 and feat1 are render_features' buffers of `feature_samples`
+        samples, rendered at the same sample_base every frame. out_a (and out_b, given exactly when
+        accum_b is) receive the integrated accumulators at 1 sample: denoise reads out_a with spp=1,
+        denoise_variance out_a and out_b with half_spp=1. Optional: out_rgba8, uint8 [band_h, band_w,
+        4], the integrated mean's bytes; history_len, a 4-byte integer tensor [band_h, band_w], the
+        frames every texel's history holds. The float tensors are float32 cuda [band_h, band_w, 4];
+        params from make_temporal() (None: the defaults). Asynchronous on `stream`, no host wait."""
+        if not isinstance(temporal, Temporal) or not temporal._state:
+            raise ValueError("temporal is closed or not a Temporal")
+        bh, bw = temporal.height, temporal.width
+        if (accum_b is None) != (out_b is None):
+            raise ValueError("give accum_b and out_b together or neither")
+        for t in (accum_a, feat0, feat1, out_a) + (() if accum_b is None else (accum_b, out_b)):
+            _check_dev_tensor(t, "torch.float32", (bh, bw, 4))
+        if (spp is None) == (sample_count is None):
+            raise ValueError("give exactly one of spp and sample_count")
+
+        def words(t, name):
+            if t is None:
+                return None
+            if not t.is_cuda or t.element_size() != 4 or t.is_floating_point() or not t.is_contiguous() \
+                    or tuple(t.shape) != (bh, bw):
+                raise ValueError(f"{name} must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            return t.data_ptr()
+        count_ptr, len_ptr = words(sample_count, "sample_count"), words(history_len, "history_len")
+        rgba_ptr = None
+        if out_rgba8 is not None:
+            _check_dev_tensor(out_rgba8, "torch.uint8", (bh, bw, 4))
+            rgba_ptr = out_rgba8.data_ptr()
+        check(self._lib.rt_temporal_accumulate_device(
+            self._ctx, temporal._state, accum_a.data_ptr(), None if accum_b is None else accum_b.data_ptr(), count_ptr,
+            int(spp or 0), feat0.data_ptr(), feat1.data_ptr(), feature_samples,
+            ctypes.byref(params) if params is not None else None, out_a.data_ptr(),
+            None if out_b is None else out_b.data_ptr(), rgba_ptr, len_ptr, _stream_ptr(stream, self.device)))
+
     def render_halves(self, rci: RenderCallInfo, accum_a, accum_b, out, rows=None,
                       options: Optional[Options] = None, stream=None) -> None:
         """A frame of rci.samplesPerRenderCall = 2 h samples per pixel as the two halves
@@ -771,6 +837,43 @@ class SampleMap:
         j = min(self.info.levels, abi.SAMPLE_MAP_MAX_LEVELS)
         return {"order": order, "levels": levels[:j].copy(), "level_tiles": level_tiles[:j].copy(),
                 "quantised": quantised}
+
+
+class Temporal:
+    """The history of a temporal stage for one band on one Renderer (rt_temporal):
+    per texel the integrated colour, the number of frames it holds and the last frame's guide.
+    Renderer.temporal_accumulate feeds it one frame at a time."""
+
+    def __init__(self, renderer: Renderer, width: int, height: int):
+        self._lib = renderer._lib
+        self._state = ctypes.c_void_p()
+        self.renderer = renderer
+        self.width, self.height = int(width), int(height)
+        check(self._lib.rt_temporal_create(renderer._ctx, self.width, self.height, ctypes.byref(self._state)))
+
+    def close(self) -> None:
+        if self._state:
+            self._lib.rt_temporal_destroy(self._state)
+            self._state = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, stream=None) -> None:
+        """Empties every texel's history (rt_temporal_reset), queued on `stream` without a host wait:
+        the next temporal_accumulate is a first frame."""
+        if not self._state:
+            raise ValueError("the Temporal is closed")
+        check(self._lib.rt_temporal_reset(self._state, _stream_ptr(stream, self.renderer.device)))
 
 
 def sample_map_block_plan(counts, quantum: int = 0, unit_samples: int = 0) -> dict:

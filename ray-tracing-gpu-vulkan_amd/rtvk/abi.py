@@ -130,6 +130,12 @@ class DenoiseVariance(ctypes.Structure):
                 ("k_depth", ctypes.c_float), ("k_color", ctypes.c_float)]
 
 
+class TemporalParams(ctypes.Structure):
+    """rt_temporal_params (include/rt_mi355x.h)."""
+    _fields_ = [("max_history", ctypes.c_uint32), ("k_normal", ctypes.c_float), ("k_depth", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
 FEATURE_MAX_SAMPLES = 256    # RT_FEATURE_MAX_SAMPLES
 
 TUNING_KEYS = ("grid", "grid_scale", "grid_coop", "grid_cq", "grid_rec", "grid_full_slack", "units_per_lane",
@@ -178,6 +184,7 @@ assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and A
 assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
 assert ctypes.sizeof(Denoise) == 16
 assert ctypes.sizeof(DenoiseVariance) == 20
+assert ctypes.sizeof(TemporalParams) == 16
 
 # Every symbol include/rt_mi355x.h and include/rt_mi355x_debug.h declare: (name, restype, argtypes).
 _P, _U32, _I, _U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
@@ -235,6 +242,12 @@ EXPORTS = {
     "rt_denoise_variance_check": (_I, [ctypes.POINTER(DenoiseVariance), _U32, _U32, _U32]),
     "rt_denoise_variance_device": (_I, [_P, _P, _P, _P, _U32, _P, _P, _U32, _U32, _U32,
                                         ctypes.POINTER(DenoiseVariance), _P, _P, _P]),
+    "rt_temporal_create": (_I, [_P, _U32, _U32, ctypes.POINTER(_P)]),
+    "rt_temporal_destroy": (_I, [_P]),
+    "rt_temporal_reset": (_I, [_P, _P]),
+    "rt_temporal_check": (_I, [ctypes.POINTER(TemporalParams), _U32, _U32, _U32]),
+    "rt_temporal_accumulate_device": (_I, [_P, _P, _P, _P, _P, _U32, _P, _P, _U32, ctypes.POINTER(TemporalParams),
+                                           _P, _P, _P, _P, _P]),
     "rt_multi_create": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_multi_destroy": (_I, [_P]),
     "rt_multi_device_count": (_I, [_P, ctypes.POINTER(_U32)]),
