@@ -619,9 +619,9 @@ int rt_denoise_variance_device(rt_context* ctx, const float* accum_a, const floa
  * context it was created on and must be destroyed before it, as a sample map. rt_temporal_reset sets
  * n = 0 everywhere, queued on `stream` without a host wait: the next call is a first frame.
  * rt_temporal_check is the parameter check alone (host only, no device).
- * Not part of the stage: weighting frames by their sample counts, reprojection under camera or
- * object motion (a texel whose surface changed starts over), sharing the pass with the filters'
- * prologue.
+ * Not part of the stage: weighting frames by their sample counts, sharing the pass with the filters'
+ * prologue. This call compares a texel with itself a frame ago (a texel whose surface changed starts
+ * over); under camera or object motion use rt_temporal_reproject_device below.
  */
 typedef struct rt_temporal rt_temporal;
 typedef struct rt_temporal_params {
@@ -639,6 +639,103 @@ int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* temporal, const 
                                   const float* feat1, uint32_t feature_samples, const rt_temporal_params* params,
                                   float* out_a, float* out_b, uint8_t* out_rgba8, uint32_t* history_len,
                                   void* stream);
+
+/* ---- temporal reprojection: a motion pass and a history that follows it ------
+ * The motion pass answers, for every texel of a band, where the surface seen through the texel's
+ * CENTRE stood in the previous frame's image. A motion object (rt_motion) belongs to one context, as a
+ * temporal state does, and must be destroyed before it. It owns the pass's device scratch, one ray (6
+ * floats) and one (winner, t) answer (8 bytes) per texel of its band, and the PREVIOUS frame: its
+ * RenderCallInfo (the camera) and one float4 per sphere id whose xyz is the sphere's centre.
+ *   rt_motion_set_previous   sets the previous frame from host spheres (their geometry.xyz) and its
+ *                            RenderCallInfo; copied before the call returns, uploaded on `stream`.
+ *   rt_motion_keep_current   makes the context's current scene and `rci` the previous frame: a device
+ *                            to device copy of the scene's id-indexed centres on `stream`, ordered
+ *                            behind the scene's upload or device build. A frame loop calls
+ *                            rt_render_motion_device, then rt_motion_keep_current, every frame.
+ * Before either call the previous frame is the current one (nothing moved). Spheres only translate:
+ * sphere i of the previous frame is sphere i of this one. If the previous frame holds another number of
+ * spheres than the current scene, ids mean other spheres and every texel that hits one gets ok = 0.
+ * The previous frame's image_size must be the current one's.
+ *
+ * rt_render_motion_device writes motion_out, a DEVICE float4 per texel of the object's band: band_h
+ * contiguous image rows of band_w texels from rci->offset (no row map: the stage that reads the plane
+ * reads neighbours). Three launches on `stream`, no host wait: (1) the pinhole ray through each
+ * texel's centre, camera_ray's expressions without the jitter draws,
+ *     gx = offset.x + x;  ux = float(double(float(gx) + 0.5f) * (1.0 / double(image_size.x)));  uy likewise
+ *     to = (ulc + ux hor) - uy ver;   o = lf;   v = to - lf
+ * (2) the closest hit (id, t) of every ray by the walk `opt` selects as for a frame (accel and the
+ * walk-form words; everything else of opt is ignored, NULL: the defaults), exactly as a frame's
+ * primary ray finds it; (3) the motion, binary32, one operation per step, dot(a, b) = fma(a.z, b.z,
+ * fma(a.y, b.y, a.x b.x)), with (lf', hor', ver', ulc') the previous frame's camera and the launch
+ * constants u = ulc' - lf', wn = cross(hor', ver') = (hor'.y ver'.z - hor'.z ver'.y, ...), k = dot(u, wn),
+ * ihh = 1 / dot(hor', hor'), ivv = 1 / dot(ver', ver') computed on the host in the same arithmetic:
+ *     d   = normalize(v) = v * (1 / sqrt(dot(v, v)))
+ *     hit:   p = fma(t, d, o);  q = (p - c_now[id]) + c_prev[id];  r = q - lf'
+ *            (another sphere count in the previous frame: q = p)
+ *     miss:  r = d                                       (the sky is a point at infinity)
+ *     den = dot(r, wn);  s = k / den;  rel = s r - u
+ *     sx  = ((dot(rel, hor') ihh) float(image_size.x)) - float(offset.x)
+ *     sy  = ((-(dot(rel, ver') ivv)) float(image_size.y)) - float(offset.y)
+ *     dzm = hit ? sqrt(dot(r, r)) - t : 0       (how far the surface's distance to the camera changed)
+ *     ok  = den > 0 and sx, sy finite and not (hit and another sphere count)
+ *     motion[p] = (sx, sy, dzm, ok ? 1 : 0)
+ * (sx, sy) are band coordinates of the previous frame's image in which texel (x, y)'s centre is
+ * (x + 0.5, y + 0.5): a texel nothing moved for gets its own centre back to within rounding (far below
+ * 2^-6 of a texel, the snap of the call below). tests/motion_sim.py gives the same bits.
+ * RT_ERR_INVALID_ARGUMENT before anything is queued, with rt_last_error() naming the field: the band
+ * limits of rt_denoise_check (and a band of 0 texels for rt_motion_create), a NULL pointer, an
+ * image_size of 0, a previous frame of another image_size, a motion object of another context, an
+ * unknown accel, a call between the halves of a scene build; RT_ERR_NO_SCENE before rt_set_scene.
+ * rt_motion_check is the host-only part of these checks (no device, no context).
+ */
+typedef struct rt_motion rt_motion;
+int rt_motion_create(rt_context* ctx, uint32_t band_width, uint32_t band_height, rt_motion** out);
+int rt_motion_destroy(rt_motion* motion);
+int rt_motion_set_previous(rt_motion* motion, const Sphere* spheres, uint32_t count, const RenderCallInfo* prev_rci,
+                           void* stream);
+int rt_motion_keep_current(rt_context* ctx, rt_motion* motion, const RenderCallInfo* rci, void* stream);
+int rt_motion_check(uint32_t band_width, uint32_t band_height, const RenderCallInfo* rci,
+                    const RenderCallInfo* prev_rci);
+int rt_render_motion_device(rt_context* ctx, rt_motion* motion, const RenderCallInfo* rci, float* motion_out,
+                            const rt_options* opt, void* stream);
+
+/* rt_temporal_reproject_device is rt_temporal_accumulate_device with the history of a texel fetched
+ * from where `motion` (rt_render_motion_device's plane of the state's band) says its surface was: the
+ * arguments, the parameters, the outputs and every line of that call's arithmetic hold, except that
+ * (HA, HB, `valid`) of texel p are replaced as follows, binary32, one operation per step:
+ *     (sx, sy, dzm, ok) = motion[p];   bx = sx - 0.5;  by = sy - 0.5
+ *     jx = floor(bx + 0.5);  jy = floor(by + 0.5)
+ *     snap = |bx - jx| <= 2^-6 and |by - jy| <= 2^-6
+ *     snap:       one tap (jx, jy) of weight 1
+ *     otherwise:  ix = floor(bx);  fx = bx - ix;  gx = 1 - fx  (y likewise);
+ *                 taps (ix, iy) (ix + 1, iy) (ix, iy + 1) (ix + 1, iy + 1)
+ *                 of weights gx gy, fx gy, gx fy, fx fy, in this order
+ *     ze = z + dzm
+ *     tap q of weight w counts iff ok > 0, w > 0, q lies inside the band, HA[q].w > 0 and
+ *         (1 + k_normal dn2) (1 + k_depth (dz dz)) < 2  with dn = nrm - HG[q].xyz,
+ *         dn2 = (dn.x dn.x + dn.y dn.y) + dn.z dn.z,  dz = (ze - HG[q].w) / (ze + 1)
+ *     Wt = the sum of the counting taps' w;  S = the sum of their w HA[q] (all four components);
+ *     SB = the sum of their w HB[q].rgb: each sum starts at 0 and adds its terms in tap order, a tap
+ *     that does not count adding 0
+ *     valid = Wt > 0;   HA = S / Wt;   HB.rgb = SB / Wt              (per component; HA.w is the history's n)
+ * The snap is part of the contract, not a tuning knob: a texel whose surface did not move keeps its own
+ * history unblurred (one tap of weight 1: S / Wt is HA[q] as stored), so on a static scene the call
+ * equals rt_temporal_accumulate_device bit for bit. n, a weighted mean, need not be an integer:
+ * history_len = uint32(n') truncates. HG = (nrm, z) of the current frame, as before.
+ * The call reads neighbours, so it cannot update the planes in place: the state holds a second set of
+ * its three planes, the call reads the current set, writes the other and makes that one current.
+ * rt_temporal_accumulate_device works in place on whichever set is current and rt_temporal_reset clears
+ * it; the two calls may be mixed on one state. With one accumulator HB is neither read nor written, so
+ * the HB of the set written keeps what an earlier call left there. The second set is allocated by the
+ * state's first reprojected call, the only one that may wait on the host; every later call is one
+ * kernel launch on `stream`. Refusals as rt_temporal_accumulate_device's, and motion NULL.
+ * tests/temporal_reproject_sim.py gives the same bits.
+ */
+int rt_temporal_reproject_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a, const float* accum_b,
+                                 const uint32_t* sample_count, uint32_t spp, const float* feat0, const float* feat1,
+                                 uint32_t feature_samples, const float* motion, const rt_temporal_params* params,
+                                 float* out_a, float* out_b, uint8_t* out_rgba8, uint32_t* history_len,
+                                 void* stream);
 
 /* ---- multi-device (one process, N GPUs, RCCL over xGMI) ----------------------------- */
 typedef struct rt_multi rt_multi;

@@ -217,11 +217,35 @@ struct rt_sample_map {
 
 // The state of a temporal stage (rt_temporal_create): three float4 planes of the
 // band in one allocation, HA, HB and HG (rt_temporal_host.h), written only by the work that
-// rt_temporal_accumulate_device and rt_temporal_reset queue.
+// rt_temporal_accumulate_device, rt_temporal_reproject_device and rt_temporal_reset queue. A
+// reprojected call reads neighbours, so it writes a second set of the three planes (allocated by the
+// first such call) and makes that one current; the in-place call and the reset work on the current set.
 struct rt_temporal {
     rt_context* ctx = nullptr;
     uint32_t band_w = 0, band_h = 0;
     float* planes = nullptr;
+    float* planes2 = nullptr;
+    int cur = 0;                         // the current set: 0 = planes, 1 = planes2
+    float* set(int k) const { return k ? planes2 : planes; }
+};
+
+// The state of a motion pass (rt_motion_create): the scratch of its launches (one
+// ray and one (winner, t) answer per texel of the band) and the previous frame, its camera and one
+// float4 per sphere id whose xyz is the centre (w is not read).
+struct rt_motion {
+    rt_context* ctx = nullptr;
+    uint32_t band_w = 0, band_h = 0;
+    float* rays = nullptr;
+    uint32_t* hits = nullptr;
+    bool has_prev = false;
+    RenderCallInfo prev_rci{};
+    float* prev_geom = nullptr;          // device, prev_cap float4
+    uint64_t prev_cap = 0;
+    uint32_t prev_n = 0;
+    float* stage = nullptr;              // pinned staging of rt_motion_set_previous, stage_cap float4
+    uint64_t stage_cap = 0;
+    hipEvent_t stage_ev = nullptr;       // behind the last copy out of `stage`
+    bool stage_used = false;
 };
 
 namespace rt {

@@ -7,8 +7,9 @@
 // (rt_trace_shade.h shade_rec). The denoise is one kernel per iteration (rt_denoise.hip) by the launch
 // list of its HIP-free host half (rt_denoise_host.cpp); the variance-guided denoise likewise
 // (rt_denoise_var.hip, rt_denoise_var_host.cpp), on the same band planes of the context. The temporal
-// stage in front of them is a state object of its own and one kernel (rt_temporal.hip) by the checks
-// of its host half (rt_temporal_host.cpp).
+// stage in front of them is a state object of its own and one kernel per call (rt_temporal.hip: in
+// place, or reprojected along the motion plane of rt_motion.cpp) by the checks of its host half
+// (rt_temporal_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -256,6 +257,7 @@ extern "C" int rt_temporal_destroy(rt_temporal* temporal) {
     if (!temporal) return RT_OK;
     rt::DeviceGuard g(temporal->ctx->device);
     (void)hipFree(temporal->planes);   // waits for the queued calls that still use the planes
+    (void)hipFree(temporal->planes2);
     delete temporal;
     return RT_OK;
 }
@@ -266,34 +268,30 @@ extern "C" int rt_temporal_reset(rt_temporal* temporal, void* stream) {
     rt::DeviceGuard g(ctx->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = rt::order_on(ctx, st)) return rc;
-    RT_HIP(hipMemsetAsync(temporal->planes, 0, size_t(rt::temporal::state_bytes(temporal->band_w, temporal->band_h)), st));
+    RT_HIP(hipMemsetAsync(temporal->set(temporal->cur), 0,
+                          size_t(rt::temporal::state_bytes(temporal->band_w, temporal->band_h)), st));
     return rt::mark_issued(ctx, st);
 }
 
-extern "C" int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a,
-                                             const float* accum_b, const uint32_t* sample_count, uint32_t spp,
-                                             const float* feat0, const float* feat1, uint32_t feature_samples,
-                                             const rt_temporal_params* params, float* out_a, float* out_b,
-                                             uint8_t* out_rgba8, uint32_t* history_len, void* stream) {
-    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: ctx is NULL");
-    if (!temporal) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: temporal is NULL");
-    if (temporal->ctx != ctx)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: temporal belongs to another context");
+namespace {
+
+// The checks the two temporal calls share, before anything is queued, and their launch parameters
+// but for the state's planes.
+int temporal_setup(const std::string& who, rt_context* ctx, rt_temporal* temporal, const float* accum_a,
+                   const float* accum_b, const uint32_t* sample_count, uint32_t spp, const float* feat0,
+                   const float* feat1, uint32_t feature_samples, const rt_temporal_params* params, float* out_a,
+                   float* out_b, uint8_t* out_rgba8, uint32_t* history_len, rt::TemporalParams& K) {
+    if (!ctx) return fail(RT_ERR_INVALID_ARGUMENT, who + ": ctx is NULL");
+    if (!temporal) return fail(RT_ERR_INVALID_ARGUMENT, who + ": temporal is NULL");
+    if (temporal->ctx != ctx) return fail(RT_ERR_INVALID_ARGUMENT, who + ": temporal belongs to another context");
     rt_temporal_params p;
     const char* err = "";
     if (int rc = rt::temporal::check(params, temporal->band_w, temporal->band_h, feature_samples, &p, &err))
         return fail(rc, err);
     if (!accum_a || !feat0 || !feat1 || !out_a)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: accum_a, feat0, feat1 or out_a is NULL");
-    if (accum_b && !out_b)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: accum_b is given and out_b is NULL");
-    if (out_b && !accum_b)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_accumulate_device: out_b is given and accum_b is NULL");
-    rt::DeviceGuard g(ctx->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = rt::order_on(ctx, st)) return rc;
-    const uint64_t plane = rt::temporal::plane_floats(temporal->band_w, temporal->band_h);
-    rt::TemporalParams K;
+        return fail(RT_ERR_INVALID_ARGUMENT, who + ": accum_a, feat0, feat1 or out_a is NULL");
+    if (accum_b && !out_b) return fail(RT_ERR_INVALID_ARGUMENT, who + ": accum_b is given and out_b is NULL");
+    if (out_b && !accum_b) return fail(RT_ERR_INVALID_ARGUMENT, who + ": out_b is given and accum_b is NULL");
     std::memset(&K, 0, sizeof(K));
     K.band_w = temporal->band_w;
     K.band_h = temporal->band_h;
@@ -307,13 +305,67 @@ extern "C" int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* tempo
     K.sample_count = sample_count;
     K.feat0 = feat0;
     K.feat1 = feat1;
-    K.ha = temporal->planes;
-    K.hb = temporal->planes + plane;
-    K.hg = temporal->planes + 2u * plane;
     K.out_a = out_a;
     K.out_b = out_b;
     K.out_rgba8 = reinterpret_cast<uint32_t*>(out_rgba8);
     K.history_len = history_len;
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_temporal_accumulate_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a,
+                                             const float* accum_b, const uint32_t* sample_count, uint32_t spp,
+                                             const float* feat0, const float* feat1, uint32_t feature_samples,
+                                             const rt_temporal_params* params, float* out_a, float* out_b,
+                                             uint8_t* out_rgba8, uint32_t* history_len, void* stream) {
+    rt::TemporalParams K;
+    if (int rc = temporal_setup("rt_temporal_accumulate_device", ctx, temporal, accum_a, accum_b, sample_count, spp, feat0,
+                                feat1, feature_samples, params, out_a, out_b, out_rgba8, history_len, K))
+        return rc;
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    const uint64_t plane = rt::temporal::plane_floats(temporal->band_w, temporal->band_h);
+    float* cur = temporal->set(temporal->cur);
+    K.ha = cur;
+    K.hb = cur + plane;
+    K.hg = cur + 2u * plane;
     RT_HIP(rt::launch_temporal(K, st));
+    return rt::mark_issued(ctx, st);
+}
+
+extern "C" int rt_temporal_reproject_device(rt_context* ctx, rt_temporal* temporal, const float* accum_a,
+                                            const float* accum_b, const uint32_t* sample_count, uint32_t spp,
+                                            const float* feat0, const float* feat1, uint32_t feature_samples,
+                                            const float* motion, const rt_temporal_params* params, float* out_a,
+                                            float* out_b, uint8_t* out_rgba8, uint32_t* history_len, void* stream) {
+    rt::TemporalReprojectParams R;
+    std::memset(&R, 0, sizeof(R));
+    if (int rc = temporal_setup("rt_temporal_reproject_device", ctx, temporal, accum_a, accum_b, sample_count, spp, feat0,
+                                feat1, feature_samples, params, out_a, out_b, out_rgba8, history_len, R.T))
+        return rc;
+    if (!motion) return fail(RT_ERR_INVALID_ARGUMENT, "rt_temporal_reproject_device: motion is NULL");
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    if (!temporal->planes2) {   // the first reprojected call of the state: the one that may wait
+        const size_t bytes = size_t(rt::temporal::state_bytes(temporal->band_w, temporal->band_h));
+        ctx->host_waits++;
+        RT_HIP(hipMalloc(reinterpret_cast<void**>(&temporal->planes2), bytes));
+        RT_HIP(hipMemsetAsync(temporal->planes2, 0, bytes, st));
+    }
+    const uint64_t plane = rt::temporal::plane_floats(temporal->band_w, temporal->band_h);
+    const float* src = temporal->set(temporal->cur);
+    float* dst = temporal->set(temporal->cur ^ 1);
+    R.motion = motion;
+    R.ha_src = src;
+    R.hb_src = src + plane;
+    R.hg_src = src + 2u * plane;
+    R.T.ha = dst;
+    R.T.hb = dst + plane;
+    R.T.hg = dst + 2u * plane;
+    RT_HIP(rt::launch_temporal_reproject(R, st));
+    temporal->cur ^= 1;
     return rt::mark_issued(ctx, st);
 }

@@ -43,6 +43,12 @@
 //   on one stream; prints duration_per_frame; --store writes the last frame's filtered image. Refused
 //   without a filter, without --frames, with --gpus above 1, with --adaptive, without --rng hash, and
 //   when K x --samples does not fit 32 bits.
+//   --reproject: beside --temporal, every frame also renders its motion plane against the frame before
+//   (rt_render_motion_device, then rt_motion_keep_current) and the history follows it
+//   (rt_temporal_reproject_device in place of rt_temporal_accumulate_device). Refused without --temporal.
+//   --camera-step S: frame k's camera stands at (13 + S k, 11, -3 + 2 S k) and looks at the origin
+//   (default 0: the reference's camera every frame), with or without --reproject. Refused without
+//   --temporal.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -426,9 +432,11 @@ int run_adaptive_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
 // filter's dn. The stored image is the last frame's filtered one.
 int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate, bool store,
                         uint32_t feature_samples, const rt_denoise& dn, const rt_denoise_variance* dv,
-                        const rt_temporal_params& tp) {
+                        const rt_temporal_params& tp, bool reproject, float camera_step) {
     rt_context* ctx = nullptr;
     rt_temporal* temporal = nullptr;
+    rt_motion* motion = nullptr;
+    float* motion_plane = nullptr;
     hipStream_t stream = nullptr;
     float *accum_a = nullptr, *accum_b = nullptr, *feat0 = nullptr, *feat1 = nullptr, *out_a = nullptr, *out_b = nullptr;
     uint8_t* rgba8 = nullptr;
@@ -447,6 +455,10 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     CLI_HIP(hipMalloc(&feat0, texels * 16));
     CLI_HIP(hipMalloc(&feat1, texels * 16));
     CLI_HIP(hipMalloc(&rgba8, texels * 4));
+    if (reproject) {
+        CLI_RT(rt_motion_create(ctx, width, height, &motion));
+        CLI_HIP(hipMalloc(&motion_plane, texels * 16));
+    }
     rt_options feat_opt;
     std::memset(&feat_opt, 0, sizeof(feat_opt));
     feat_opt.rng_mode = RT_RNG_SAMPLE_HASH;
@@ -460,6 +472,11 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
         RenderCallInfo rci;
         CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+        if (camera_step != 0.0f) {   // frame k of the path; it looks at the origin
+            rci.camera_pos.x = 13.0f + camera_step * float(frame_index);
+            rci.camera_pos.z = -3.0f + (2.0f * camera_step) * float(frame_index);
+            rci.camera_dir = rt_vec4{-rci.camera_pos.x, -rci.camera_pos.y, -rci.camera_pos.z, 0.0f};
+        }
         rt_options opt = feat_opt;
         opt.sample_base = frame_index * samples;
         if (dv) {
@@ -473,8 +490,15 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
             CLI_RT(rt_render_device(ctx, &rci, nullptr, width, height, accum_a, rgba8, &opt, stream));
         }
         CLI_RT(rt_render_features_device(ctx, &rci, nullptr, width, height, feat0, feat1, feature_samples, &feat_opt, stream));
-        CLI_RT(rt_temporal_accumulate_device(ctx, temporal, accum_a, accum_b, nullptr, dv ? half : samples, feat0, feat1,
-                                             feature_samples, &tp, out_a, out_b, nullptr, nullptr, stream));
+        if (reproject) {
+            CLI_RT(rt_render_motion_device(ctx, motion, &rci, motion_plane, nullptr, stream));
+            CLI_RT(rt_motion_keep_current(ctx, motion, &rci, stream));
+            CLI_RT(rt_temporal_reproject_device(ctx, temporal, accum_a, accum_b, nullptr, dv ? half : samples, feat0, feat1,
+                                                feature_samples, motion_plane, &tp, out_a, out_b, nullptr, nullptr, stream));
+        } else {
+            CLI_RT(rt_temporal_accumulate_device(ctx, temporal, accum_a, accum_b, nullptr, dv ? half : samples, feat0, feat1,
+                                                 feature_samples, &tp, out_a, out_b, nullptr, nullptr, stream));
+        }
         if (dv)
             CLI_RT(rt_denoise_variance_device(ctx, out_a, out_b, nullptr, 1, feat0, feat1, feature_samples, width, height, dv,
                                               nullptr, rgba8, stream));
@@ -501,10 +525,10 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         CLI_HIP(hipStreamSynchronize(stream));
         const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
         done += k;
-        std::printf("duration_per_frame: %.3f ms (%u frames, %u spp%s, temporal history %u, %s denoise: %u feature samples, "
+        std::printf("duration_per_frame: %.3f ms (%u frames, %u spp%s, temporal history %u%s, %s denoise: %u feature samples, "
                     "%.1f Msamples/s)\n",
-                    sec / k * 1e3, k, samples, dv ? " in two halves" : "", tp.max_history, dv ? "variance-guided" : "plain",
-                    feature_samples, double(width) * height * samples * k / sec / 1e6);
+                    sec / k * 1e3, k, samples, dv ? " in two halves" : "", tp.max_history, reproject ? " reprojected" : "",
+                    dv ? "variance-guided" : "plain", feature_samples, double(width) * height * samples * k / sec / 1e6);
     }
     if (store) {   // the last frame
         std::vector<uint8_t> img(texels * 4);
@@ -512,8 +536,10 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
         CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
     }
     rt_temporal_destroy(temporal);
+    rt_motion_destroy(motion);
     rt_context_destroy(ctx);
     (void)hipStreamDestroy(stream);
+    (void)hipFree(motion_plane);
     (void)hipFree(accum_a);
     (void)hipFree(accum_b);
     (void)hipFree(out_a);
@@ -575,6 +601,8 @@ int main(int argc, const char** argv) {
     rt_denoise_variance dv = {3u, 2u, 4.0f, 16.0f, 0.25f};
     bool temporal = false;
     rt_temporal_params tp = {8u, 4.0f, 16.0f, 0u};
+    bool reproject = false, camera_step_given = false;
+    float camera_step = 0.0f;
     rt_adaptive ad;
     std::memset(&ad, 0, sizeof(ad));
     for (int i = 1; i < argc; i++) {
@@ -607,6 +635,10 @@ int main(int argc, const char** argv) {
             std::puts("--temporal [<N>]                  # With --frames and --denoise or --denoise-variance: every frame takes");
             std::puts("                                  # a sample range of its own and is integrated into a per-pixel");
             std::puts("                                  # history of at most N frames (default 8) ahead of the filter");
+            std::puts("--reproject                       # With --temporal: a motion pass per frame, and the history follows");
+            std::puts("                                  # camera and sphere motion instead of staying in place");
+            std::puts("--camera-step <S>                 # With --temporal: frame k's camera at (13 + S k, 11, -3 + 2 S k),");
+            std::puts("                                  # looking at the origin (default 0)");
             return 0;
         } else if (a == "--adaptive") {
             if (i + 1 >= argc || !parse_adaptive(argv[i + 1], ad)) {
@@ -642,6 +674,18 @@ int main(int argc, const char** argv) {
                 }
                 ++i;
             }
+        } else if (a == "--reproject") {
+            reproject = true;
+        } else if (a == "--camera-step") {
+            char* end = nullptr;
+            if (i + 1 < argc) camera_step = std::strtof(argv[i + 1], &end);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(camera_step == camera_step) ||
+                camera_step - camera_step != 0.0f) {
+                std::fprintf(stderr, "--camera-step needs a finite number\n");
+                return 2;
+            }
+            ++i;
+            camera_step_given = true;
         } else if (a == "--store") {
             store = true;
         } else if (a == "--feedback") {
@@ -705,6 +749,14 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--adaptive renders on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
+    }
+    if (reproject && !temporal) {
+        std::fprintf(stderr, "--reproject moves the history of --temporal: it needs --temporal\n");
+        return 2;
+    }
+    if (camera_step_given && !temporal) {
+        std::fprintf(stderr, "--camera-step moves the camera of the --temporal frame loop: it needs --temporal\n");
+        return 2;
     }
     if (temporal) {   // refused before anything renders
         if (!denoise && !denoise_variance) {
@@ -795,7 +847,7 @@ int main(int argc, const char** argv) {
         const rt_denoise dn = {denoise_iterations, 4.0f, 16.0f, 1.0f};
         return run_temporal_frames(samples, width, height, frames, animate, store,
                                    denoise_variance ? dv_feature_samples : feature_samples, dn,
-                                   denoise_variance ? &dv : nullptr, tp);
+                                   denoise_variance ? &dv : nullptr, tp, reproject, camera_step);
     }
     if (denoise_variance) return run_denoised_variance(samples, width, height, store, dv_feature_samples, dv);
     if (denoise) return run_denoised(samples, width, height, store, adaptive ? &ad : nullptr, feature_samples, denoise_iterations);

@@ -30,7 +30,18 @@ struct TemporalParams {
     uint32_t* history_len;          // optional
 };
 
+// rt_temporal_reproject_device's one launch: T as above with ha / hb / hg the plane set the call
+// WRITES, and the set it reads its history taps from, which must be another one.
+struct TemporalReprojectParams {
+    TemporalParams T;
+    const float* motion;            // float4 per texel (sx, sy, dzm, ok)
+    const float* ha_src;
+    const float* hb_src;
+    const float* hg_src;
+};
+
 // One launch of one thread per texel; the two-accumulator instantiation when K.accum_b is set.
 hipError_t launch_temporal(const TemporalParams& K, hipStream_t st);
+hipError_t launch_temporal_reproject(const TemporalReprojectParams& K, hipStream_t st);
 
 }  // namespace rt

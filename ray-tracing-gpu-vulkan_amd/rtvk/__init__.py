@@ -32,7 +32,7 @@ __all__ = [
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
     "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
     "make_denoise", "denoise_check", "make_denoise_variance", "denoise_variance_check",
-    "Temporal", "make_temporal", "temporal_check",
+    "Temporal", "make_temporal", "temporal_check", "Motion", "motion_check",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -534,25 +534,16 @@ class Renderer:
         self._maps.add(t)   # closed with the renderer at the latest
         return t
 
-    def temporal_accumulate(self, temporal: "Temporal", accum_a, feat0, feat1, feature_samples: int, out_a,
-                            accum_b=None, out_b=None, out_rgba8=None, history_len=None, spp: Optional[int] = None,
-                            sample_count=None, params: Optional["abi.TemporalParams"] = None, stream=None) -> None:
-        """One frame into `temporal`'s history (rt_temporal_accumulate_device): accum_a (and accum_b,
-        a frame rendered as two halves) are summed accumulators of the temporal's band, each texel
-        holding `spp` samples or those of the 4-byte integer cuda tensor sample_count [band_h, band_w]
-        (exactly one of them); feat0 and feat1 are render_features' buffers of `feature_samples`
-        samples, rendered at the same sample_base every frame. out_a (and out_b, given exactly when
-        accum_b is) receive the integrated accumulators at 1 sample: denoise reads out_a with spp=1,
-        denoise_variance out_a and out_b with half_spp=1. Optional: out_rgba8, uint8 [band_h, band_w,
-        4], the integrated mean's bytes; history_len, a 4-byte integer tensor [band_h, band_w], the
-        frames every texel's history holds. The float tensors are float32 cuda [band_h, band_w, 4];
-        params from make_temporal() (None: the defaults). Asynchronous on `stream`, no host wait."""
+    @staticmethod
+    def _temporal_pointers(temporal, floats, accum_b, out_b, out_rgba8, history_len, spp, sample_count):
+        """The tensor checks the two temporal calls share; `floats` are their required float32 planes.
+        Returns the pointers (sample_count, out_rgba8, history_len), None for what is not given."""
         if not isinstance(temporal, Temporal) or not temporal._state:
             raise ValueError("temporal is closed or not a Temporal")
         bh, bw = temporal.height, temporal.width
         if (accum_b is None) != (out_b is None):
             raise ValueError("give accum_b and out_b together or neither")
-        for t in (accum_a, feat0, feat1, out_a) + (() if accum_b is None else (accum_b, out_b)):
+        for t in tuple(floats) + (() if accum_b is None else (accum_b, out_b)):
             _check_dev_tensor(t, "torch.float32", (bh, bw, 4))
         if (spp is None) == (sample_count is None):
             raise ValueError("give exactly one of spp and sample_count")
@@ -569,9 +560,64 @@ class Renderer:
         if out_rgba8 is not None:
             _check_dev_tensor(out_rgba8, "torch.uint8", (bh, bw, 4))
             rgba_ptr = out_rgba8.data_ptr()
+        return count_ptr, rgba_ptr, len_ptr
+
+    def temporal_accumulate(self, temporal: "Temporal", accum_a, feat0, feat1, feature_samples: int, out_a,
+                            accum_b=None, out_b=None, out_rgba8=None, history_len=None, spp: Optional[int] = None,
+                            sample_count=None, params: Optional["abi.TemporalParams"] = None, stream=None) -> None:
+        """One frame into `temporal`'s history (rt_temporal_accumulate_device): accum_a (and accum_b,
+        a frame rendered as two halves) are summed accumulators of the temporal's band, each texel
+        holding `spp` samples or those of the 4-byte integer cuda tensor sample_count [band_h, band_w]
+        (exactly one of them); feat0 and feat1 are render_features' buffers of `feature_samples`
+        samples, rendered at the same sample_base every frame. out_a (and out_b, given exactly when
+        accum_b is) receive the integrated accumulators at 1 sample: denoise reads out_a with spp=1,
+        denoise_variance out_a and out_b with half_spp=1. Optional: out_rgba8, uint8 [band_h, band_w,
+        4], the integrated mean's bytes; history_len, a 4-byte integer tensor [band_h, band_w], the
+        frames every texel's history holds. The float tensors are float32 cuda [band_h, band_w, 4];
+        params from make_temporal() (None: the defaults). Asynchronous on `stream`, no host wait."""
+        count_ptr, rgba_ptr, len_ptr = self._temporal_pointers(temporal, (accum_a, feat0, feat1, out_a), accum_b, out_b,
+                                                               out_rgba8, history_len, spp, sample_count)
         check(self._lib.rt_temporal_accumulate_device(
             self._ctx, temporal._state, accum_a.data_ptr(), None if accum_b is None else accum_b.data_ptr(), count_ptr,
             int(spp or 0), feat0.data_ptr(), feat1.data_ptr(), feature_samples,
+            ctypes.byref(params) if params is not None else None, out_a.data_ptr(),
+            None if out_b is None else out_b.data_ptr(), rgba_ptr, len_ptr, _stream_ptr(stream, self.device)))
+
+    def motion(self, width: int, height: int) -> "Motion":
+        """The state of a motion pass for a band of width x height texels on this context
+        (rt_motion_create): its scratch and the previous frame, which is the current one until
+        set_previous or keep_current says otherwise. Close it before the renderer."""
+        m = Motion(self, width, height)
+        self._maps.add(m)   # closed with the renderer at the latest
+        return m
+
+    def render_motion(self, motion: "Motion", rci: RenderCallInfo, motion_out, options: Optional[Options] = None,
+                      stream=None) -> None:
+        """Where the surface seen through each texel's centre stood in the previous frame's image
+        (rt_render_motion_device): motion_out, a float32 cuda tensor [band_h, band_w, 4] of the
+        motion's band (contiguous image rows from rci.offset), receives (sx, sy, dzm, ok) per texel,
+        sx and sy in band coordinates with texel centres at + 0.5. options selects the walk as for a
+        frame. Asynchronous on `stream`, no host wait."""
+        if not isinstance(motion, Motion) or not motion._state:
+            raise ValueError("motion is closed or not a Motion")
+        _check_dev_tensor(motion_out, "torch.float32", (motion.height, motion.width, 4))
+        check(self._lib.rt_render_motion_device(self._ctx, motion._state, ctypes.byref(rci), motion_out.data_ptr(),
+                                                ctypes.byref(options) if options is not None else None,
+                                                _stream_ptr(stream, self.device)))
+
+    def temporal_reproject(self, temporal: "Temporal", accum_a, feat0, feat1, feature_samples: int, motion, out_a,
+                           accum_b=None, out_b=None, out_rgba8=None, history_len=None, spp: Optional[int] = None,
+                           sample_count=None, params: Optional["abi.TemporalParams"] = None, stream=None) -> None:
+        """temporal_accumulate with every texel's history fetched from where `motion` (render_motion's
+        float32 cuda tensor [band_h, band_w, 4] of the same band) says its surface was
+        (rt_temporal_reproject_device): one tap where nothing moved, four bilinear taps elsewhere,
+        each checked against the guide. The other arguments are temporal_accumulate's. The state's
+        first reprojected call allocates its second plane set; later ones queue one launch."""
+        count_ptr, rgba_ptr, len_ptr = self._temporal_pointers(temporal, (accum_a, feat0, feat1, motion, out_a), accum_b,
+                                                               out_b, out_rgba8, history_len, spp, sample_count)
+        check(self._lib.rt_temporal_reproject_device(
+            self._ctx, temporal._state, accum_a.data_ptr(), None if accum_b is None else accum_b.data_ptr(), count_ptr,
+            int(spp or 0), feat0.data_ptr(), feat1.data_ptr(), feature_samples, motion.data_ptr(),
             ctypes.byref(params) if params is not None else None, out_a.data_ptr(),
             None if out_b is None else out_b.data_ptr(), rgba_ptr, len_ptr, _stream_ptr(stream, self.device)))
 
@@ -874,6 +920,62 @@ class Temporal:
         if not self._state:
             raise ValueError("the Temporal is closed")
         check(self._lib.rt_temporal_reset(self._state, _stream_ptr(stream, self.renderer.device)))
+
+
+class Motion:
+    """The state of a motion pass for one band on one Renderer (rt_motion): the
+    pass's device scratch and the previous frame, its camera and sphere centres.
+    Renderer.render_motion reads it; a frame loop calls render_motion, then keep_current."""
+
+    def __init__(self, renderer: Renderer, width: int, height: int):
+        self._lib = renderer._lib
+        self._state = ctypes.c_void_p()
+        self.renderer = renderer
+        self.width, self.height = int(width), int(height)
+        check(self._lib.rt_motion_create(renderer._ctx, self.width, self.height, ctypes.byref(self._state)))
+
+    def close(self) -> None:
+        if self._state:
+            self._lib.rt_motion_destroy(self._state)
+            self._state = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_previous(self, spheres, prev_rci: RenderCallInfo, stream=None) -> None:
+        """The previous frame given explicitly (rt_motion_set_previous): its spheres (ctypes Sphere
+        array or (n, 80) uint8 records, as Renderer.set_scene takes them) and its RenderCallInfo."""
+        if not self._state:
+            raise ValueError("the Motion is closed")
+        buf = spheres if not isinstance(spheres, np.ndarray) else np.ascontiguousarray(spheres, np.uint8)
+        n = len(spheres)
+        ptr = ctypes.addressof(buf) if not isinstance(buf, np.ndarray) else buf.ctypes.data
+        check(self._lib.rt_motion_set_previous(self._state, ptr if n else None, n, ctypes.byref(prev_rci),
+                                               _stream_ptr(stream, self.renderer.device)))
+
+    def keep_current(self, rci: RenderCallInfo, stream=None) -> None:
+        """The renderer's current scene and `rci` become the previous frame (rt_motion_keep_current),
+        queued on `stream` behind the scene's upload or build."""
+        if not self._state:
+            raise ValueError("the Motion is closed")
+        check(self._lib.rt_motion_keep_current(self.renderer._ctx, self._state, ctypes.byref(rci),
+                                               _stream_ptr(stream, self.renderer.device)))
+
+
+def motion_check(band_w: int, band_h: int, rci: Optional[RenderCallInfo], prev_rci: Optional[RenderCallInfo] = None) -> None:
+    """rt_motion_check (host only): raises RtError where Renderer.render_motion would refuse its band
+    or its two RenderCallInfo."""
+    check(load_library().rt_motion_check(band_w, band_h, ctypes.byref(rci) if rci is not None else None,
+                                         ctypes.byref(prev_rci) if prev_rci is not None else None))
 
 
 def sample_map_block_plan(counts, quantum: int = 0, unit_samples: int = 0) -> dict:

@@ -248,6 +248,14 @@ EXPORTS = {
     "rt_temporal_check": (_I, [ctypes.POINTER(TemporalParams), _U32, _U32, _U32]),
     "rt_temporal_accumulate_device": (_I, [_P, _P, _P, _P, _P, _U32, _P, _P, _U32, ctypes.POINTER(TemporalParams),
                                            _P, _P, _P, _P, _P]),
+    "rt_motion_create": (_I, [_P, _U32, _U32, ctypes.POINTER(_P)]),
+    "rt_motion_destroy": (_I, [_P]),
+    "rt_motion_set_previous": (_I, [_P, _P, _U32, ctypes.POINTER(RenderCallInfo), _P]),
+    "rt_motion_keep_current": (_I, [_P, _P, ctypes.POINTER(RenderCallInfo), _P]),
+    "rt_motion_check": (_I, [_U32, _U32, ctypes.POINTER(RenderCallInfo), ctypes.POINTER(RenderCallInfo)]),
+    "rt_render_motion_device": (_I, [_P, _P, ctypes.POINTER(RenderCallInfo), _P, ctypes.POINTER(Options), _P]),
+    "rt_temporal_reproject_device": (_I, [_P, _P, _P, _P, _P, _U32, _P, _P, _U32, _P, ctypes.POINTER(TemporalParams),
+                                          _P, _P, _P, _P, _P]),
     "rt_multi_create": (_I, [_U32, ctypes.POINTER(_P)]),
     "rt_multi_destroy": (_I, [_P]),
     "rt_multi_device_count": (_I, [_P, ctypes.POINTER(_U32)]),
