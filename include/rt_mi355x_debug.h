@@ -36,7 +36,8 @@ int rt_debug_kernel_times(rt_context* ctx, float* out_ms, uint32_t capacity, uin
  * candidate queue), "grid_rec" (0: no
  * shading records in LDS), "grid_full_slack", "units_per_lane", "unit_min_samples",
  * "sample_chunks", "head_chunks", "tail_tiles_pm", "schedule" (0 LPT, 1 row-major, 2 LPT by tile
- * sum), "refill_reserve", "isolate_tiles", "sah_knobs". Unknown keys: RT_ERR_INVALID_ARGUMENT.
+ * sum), "refill_reserve", "isolate_tiles", "sah_knobs", "camera_batches" (0: the unit loop instead
+ * of the camera-batch form of the LDS grid kernel). Unknown keys: RT_ERR_INVALID_ARGUMENT.
  * Scene-build keys (grid, grid_scale, sah_knobs) apply from the next rt_set_scene. Values other
  * than -1 must be finite and within [0, 2^32]: RT_ERR_INVALID_ARGUMENT otherwise. The library
  * reads no environment variable for any of them. */
@@ -45,7 +46,8 @@ int rt_debug_tune(rt_context* ctx, const char* key, double value);
  * tiles; high 16 bits: of its head tiles, 0 when the launch had no head), the kernel form it ran
  * (low 16 bits: rt_internal.h ACCEL_*, before any launch the scene's default form; bit 16: its
  * grid walk was the one-layer form, the grid one cell thick in y; bit 17: its camera rays started
- * at the camera position itself, the pinhole shortcut), its dynamic LDS bytes, CU count}. */
+ * at the camera position itself, the pinhole shortcut; bit 18: it ran the camera-batch form of the
+ * LDS grid kernel), its dynamic LDS bytes, CU count}. */
 int rt_debug_launch_info(rt_context* ctx, uint32_t* out4);
 /* The single-device launch plan (csrc/rt_launch.h): every host decision that shapes a trace launch,
  * as a function of plain inputs. `inputs` is an rt::launch::Inputs and `plan` an rt::launch::Plan,
@@ -62,6 +64,16 @@ int rt_debug_launch_info(rt_context* ctx, uint32_t* out4);
  * adaptive frame: its last pass, whose tile list is not part of the inputs.) RT_ERR_INVALID_ARGUMENT
  * before the first launch of a scene. */
 int rt_debug_launch_plan(rt_context* ctx, void* inputs, uint64_t in_bytes, void* plan, uint64_t plan_bytes);
+/* Whether rt_render_device runs the camera-batch form of the LDS grid kernel (csrc/rt_launch.h
+ * camera_batches) for the launch that rt_debug_launch_plan(NULL, inputs, ...) plans.
+ * Host only. tune: the value of rt_debug_tune's "camera_batches" (-1: the default); max_depth: the
+ * options' (0: 50); table: a block-table launch; kernel_blocks: blocks per CU of the form's kernel
+ * as the device answers (< 0: not asked). out3 = {0 when the form is taken, else the first reason
+ * against it (rt_launch.h BATCH_OFF_*: 1 the tuning value, 2 not the counter-based stream, 3 a table
+ * launch, 4 instrumented, 5 another kernel form, 6 no pinhole_lf, 7 max_depth, 8 the two-block LDS
+ * budget, 9 the kernel's occupancy), the kernel's static LDS bytes, static + dynamic LDS bytes}. */
+int rt_debug_camera_batches(void* inputs, uint64_t in_bytes, double tune, uint32_t max_depth, uint32_t table,
+                            int kernel_blocks, uint32_t* out3);
 /* The per-row weights rt_launch_row_weights derives from a launch's tile-cost record (csrc/rt_launch.h
  * row_weights), on hand-made arrays. Host only. cost: n tile records, row-major, tiles_x per tile
  * row; order: the n tiles in the order they were handed out, or NULL; head_tiles / head_chunks /

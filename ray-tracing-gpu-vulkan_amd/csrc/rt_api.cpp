@@ -1104,9 +1104,11 @@ int launch_units(rt_context* ctx, TraceSetup& S, hipStream_t st) {
                                    const_cast<rt::TabSize*>(P.tab_size), P.counters, st));
     P.big_tab = ctx->big_tab;
     RT_HIP(hipEventRecord(kev[0], st));
-    RT_HIP(rt::launch_trace(P, accel, plan.count != 0, int(plan.mode), int(plan.grid), plan.lds, st));
+    if (S.camera_batches) RT_HIP(rt::launch_trace_batch(P, int(plan.grid), plan.lds, st));
+    else RT_HIP(rt::launch_trace(P, accel, plan.count != 0, int(plan.mode), int(plan.grid), plan.lds, st));
     RT_HIP(hipEventRecord(kev[1], st));
     ctx->kev_count++;
+    ctx->last_camera_batches = S.camera_batches;
     ctx->last_plan = plan;
     ctx->last_in = S.in;
     return RT_OK;
@@ -1205,6 +1207,25 @@ int rt_render_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t*
         sc.rec_head_tiles[sc.cur] = P.head_tiles;
         sc.rec_head_chunks[sc.cur] = P.head_chunks;
         sc.rec_chunks[sc.cur] = P.chunks;
+    }
+    {   // the camera-batch form of the headline kernel (rt_launch.h camera_batches): the plan's
+        // conditions first, then the kernel's own occupancy and static LDS at the plan's dynamic bytes
+        uint32_t total = 0;
+        uint32_t why = rt::launch::camera_batches(S.in, S.plan, ctx->tune_camera_batches, P.max_depth, false,
+                                                  rt::launch::kBatchStaticLdsBytes, -1, &total);
+        if (why == rt::launch::BATCH_ON) {
+            if (ctx->batch_occ_lds != S.plan.lds) {
+                int b = 0;
+                size_t stat = 0;
+                RT_HIP(rt::trace_batch_occupancy(S.plan.lds, &b, &stat));
+                ctx->batch_occ = stat == rt::launch::kBatchStaticLdsBytes ? b : 0;   // (a kernel whose LDS the
+                                                                                     // plan does not describe: off)
+                ctx->batch_occ_lds = S.plan.lds;
+            }
+            why = rt::launch::camera_batches(S.in, S.plan, ctx->tune_camera_batches, P.max_depth, false,
+                                             rt::launch::kBatchStaticLdsBytes, ctx->batch_occ, &total);
+        }
+        S.camera_batches = why == rt::launch::BATCH_ON;
     }
     if (int rc = launch_units(ctx, S, st)) return rc;
     if (mode == rt::MODE_HASH)
@@ -1469,6 +1490,10 @@ int rt_debug_tune(rt_context* ctx, const char* key, double value) {
     if (!ctx || !key) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!rt::launch::tuning_value_ok(value))
         return fail(RT_ERR_INVALID_ARGUMENT, "tuning values are finite, >= 0 and <= 2^32 (-1 restores the default)");
+    if (std::strcmp(key, "camera_batches") == 0) {   // (beside ctx->tune: rt_context.h)
+        ctx->tune_camera_batches = value;
+        return RT_OK;
+    }
     double Tuning::*field = rt::launch::tuning_field(key);
     if (!field) return fail(RT_ERR_INVALID_ARGUMENT, std::string("unknown tuning key ") + key);
     ctx->tune.*field = value;
@@ -1480,7 +1505,8 @@ int rt_debug_launch_info(rt_context* ctx, uint32_t* out4) {
     const rt::launch::Plan& p = ctx->last_plan;
     out4[0] = p.chunks | (p.head_tiles ? p.head_chunks << 16 : 0u);
     if (p.accel) {   // the kernel form the last launch actually ran
-        out4[1] = p.accel | (p.flat ? 0x10000u : 0u) | (ctx->last_in.pinhole_lf ? 0x20000u : 0u);
+        out4[1] = p.accel | (p.flat ? 0x10000u : 0u) | (ctx->last_in.pinhole_lf ? 0x20000u : 0u) |
+                  (ctx->last_camera_batches ? 0x40000u : 0u);
         out4[2] = p.lds;
     } else {   // no launch yet: the default form of the current scene (camera within its pad radius)
         rt::launch::Inputs in;
@@ -1526,6 +1552,22 @@ int rt_debug_launch_plan(rt_context* ctx, void* inputs, uint64_t in_bytes, void*
     const char* err = "";
     if (int rc = rt::launch::make_plan(in, rt::launch::table_device(in), p, &err)) return fail(rc, err);
     std::memcpy(plan, &p, sizeof(p));
+    return RT_OK;
+}
+
+int rt_debug_camera_batches(void* inputs, uint64_t in_bytes, double tune, uint32_t max_depth, uint32_t table,
+                            int kernel_blocks, uint32_t* out3) {
+    if (!out3) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!rt::launch::tuning_value_ok(tune)) return fail(RT_ERR_INVALID_ARGUMENT, "tuning value out of range: camera_batches");
+    rt::launch::Plan p;
+    if (int rc = rt_debug_launch_plan(nullptr, inputs, in_bytes, &p, sizeof(p))) return rc;
+    rt::launch::Inputs in;
+    std::memcpy(&in, inputs, sizeof(in));
+    uint32_t total = 0;
+    out3[0] = rt::launch::camera_batches(in, p, tune, max_depth ? max_depth : 50u, table != 0u,
+                                         rt::launch::kBatchStaticLdsBytes, kernel_blocks, &total);
+    out3[1] = rt::launch::kBatchStaticLdsBytes;
+    out3[2] = total;
     return RT_OK;
 }
 

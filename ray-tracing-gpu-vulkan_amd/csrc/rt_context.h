@@ -36,6 +36,7 @@ struct TraceSetup {
     rt::launch::Plan plan;       // the form half (plan_form); split_units fills the rest per launch
     uint64_t tiles_x = 0, n_tiles = 0;
     const uint32_t* tab_blocks = nullptr;   // with P.tab_size: the device word that holds the table's block count
+    bool camera_batches = false;            // launch_units runs the camera-batch form (rt_render_device's decision)
 };
 
 struct rt_context {
@@ -111,6 +112,13 @@ struct rt_context {
     // the occupancies it queried (rt_debug_launch_info, rt_debug_launch_plan)
     rt::launch::Plan last_plan;
     rt::launch::Inputs last_in;
+    // the camera-batch form (rt_launch.h camera_batches): its tuning value (rt_debug_tune
+    // "camera_batches"; kept beside `tune`, whose layout is part of the plan's inputs), the occupancy
+    // of its kernel at batch_occ_lds dynamic bytes, and whether the last launch ran it
+    double tune_camera_batches = rt::launch::Tuning::kUnset;
+    int batch_occ = 0;
+    size_t batch_occ_lds = ~size_t(0);
+    bool last_camera_batches = false;
     // every colour the shaders can return lies in [0, 1] (RT_RNG_SAMPLE_HASH's fixed point needs it)
     bool colours_unit = true;
     // host waits inside render and set calls that are documented as queued without one (buffer

@@ -99,6 +99,14 @@ constexpr unsigned kCoopLdsBytes = (2u * 16u + 8u + 4u) * RT_TRACE_BLOCK;
 // Wave-wide candidate queue (ACCEL_GRID_CQ / ACCEL_GRID_REC_CQ): 128 queue entries (u32) and a
 // count per wave, a key (u64) per thread.
 constexpr unsigned kCqLdsBytes = (128u * 4u + 4u) * (RT_TRACE_BLOCK / 64u) + 8u * RT_TRACE_BLOCK;
+// Camera-batch form of the LDS grid kernel (rt_trace_batch.h): per wave a queue of kBatchQueue
+// paths (44 B each: o, LCG state, d, pixel | depth, thr) and a chain counter per pixel of its tile,
+// beside the kLaneSumLdsBytes sums (one slot per pixel there). The form reads the winner's records
+// from L2: the static record table does not fit beside the queue in a two-block budget.
+constexpr unsigned kBatchQueue = 64u;
+constexpr unsigned kBatchLdsBytes = (4u + 16u + 16u + 12u) * RT_TRACE_BLOCK;
+// A queue entry's word holds the path's depth above the pixel's 6 bits.
+constexpr uint32_t kBatchMaxDepth = 1u << 26;
 
 // Scene as resident in HBM (one allocation per context, rebuilt by rt_set_scene).
 struct DeviceScene {

@@ -30,6 +30,7 @@
 #include "rt_trace_shade.h"
 #include "rt_trace_walk.h"
 #include "rt_trace_grid_coop.h"
+#include "rt_trace_batch.h"
 
 using namespace rtd;
 
@@ -378,6 +379,32 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
                                         reinterpret_cast<const float4*>(P.mat));
 }
 
+// Camera-batch form of the LDS grid kernel (rt_trace_batch.h): HASH launches with the uniform
+// hand-out whose plan proved pinhole_lf and a two-block LDS budget (launch_trace_batch's callers). The
+// grid is staged as in rt_trace_grid_kernel; the winner's gate and shading records come from L2
+// (the static table s_rec does not fit beside the path queue). A kernel of its own, so that every
+// other kernel keeps its name and its code.
+template <bool FLAT>
+__global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace_grid_batch_kernel(const rt::TraceParams P) {
+    UTIL_INIT;
+    PLACEMENT_RECORD(P);
+    extern __shared__ float4 lds[];
+    const uint32_t nr = P.grid.n_refs, nc1 = P.grid.n_cells + 1u;
+    const uint32_t n_id4 = (nr + 3u) / 4u;
+    const float4* rec = reinterpret_cast<const float4*>(P.grid_rec);
+    for (uint32_t i = threadIdx.x; i < nr; i += kTraceBlock) lds[i] = rec[i];
+    uint32_t* ids = reinterpret_cast<uint32_t*>(lds + nr);
+    for (uint32_t i = threadIdx.x; i < nr; i += kTraceBlock) ids[i] = P.grid_ids[i];
+    uint32_t* cst = reinterpret_cast<uint32_t*>(lds + nr + n_id4);
+    for (uint32_t i = threadIdx.x; i < nc1; i += kTraceBlock) cst[i] = P.cell_start[i];
+    stage_walk_params(P, threadIdx.x);
+    stage_rows(P, threadIdx.x, kTraceBlock);
+    __syncthreads();
+    batch_loop<FLAT>(P, reinterpret_cast<const float4*>(cst), lds, ids, reinterpret_cast<const float4*>(P.geom),
+                     reinterpret_cast<const float4*>(P.mat));
+    UTIL_FLUSH;
+}
+
 // LBVH kernel for trees too big for LDS: the treelet (rt_build.hip build_treelet) is staged in LDS
 // with its rank links turned into LDS addresses; leaves, subtrees below the cut, geometry and
 // materials stay in HBM/L2.
@@ -491,6 +518,23 @@ hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mo
 hipError_t trace_occupancy(uint32_t accel, bool count, int mode, bool flat, size_t lds_bytes, int* blocks_per_cu) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, pick(accel, count, mode, flat),
                                                         block_size(accel), lds_bytes);
+}
+
+// The camera-batch form (rt_trace_batch.h): the one-layer LDS grid walk of a HASH launch with the
+// uniform hand-out; the plan decides (rt_launch.h camera_batches), rt_render_device launches.
+hipError_t launch_trace_batch(const TraceParams& P, int grid, size_t lds_bytes, hipStream_t st) {
+    void* args[] = {const_cast<TraceParams*>(&P)};
+    return hipLaunchKernel(reinterpret_cast<const void*>(rt_trace_grid_batch_kernel<true>), dim3(grid), dim3(kTraceBlock),
+                           args, lds_bytes, st);
+}
+
+hipError_t trace_batch_occupancy(size_t lds_bytes, int* blocks_per_cu, size_t* static_lds) {
+    hipFuncAttributes a;
+    if (hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(rt_trace_grid_batch_kernel<true>)); e != hipSuccess)
+        return e;
+    *static_lds = a.sharedSizeBytes;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks_per_cu, reinterpret_cast<const void*>(rt_trace_grid_batch_kernel<true>), kTraceBlock, lds_bytes);
 }
 
 }  // namespace rt

@@ -333,6 +333,22 @@ void hand_out_units(const Inputs& in, Plan& P, bool tile_order) {
     }
 }
 
+uint32_t camera_batches(const Inputs& in, const Plan& p, double tune, uint32_t max_depth, bool table,
+                        uint32_t static_lds, int kernel_blocks, uint32_t* lds_total) {
+    *lds_total = static_lds + p.lds;
+    if (Tuning::get(tune, kCameraBatchesDefault) == 0) return BATCH_OFF_TUNE;
+    if (p.mode != uint32_t(rt::MODE_HASH)) return BATCH_OFF_STREAM;
+    if (table) return BATCH_OFF_TABLE;
+    if (p.count) return BATCH_OFF_COUNT;
+    if (p.accel != rt::ACCEL_GRID_REC || !p.flat) return BATCH_OFF_FORM;   // (the L2 grid, the trees, brute force,
+                                                                           // the A/B forms, a grid of several layers)
+    if (!in.pinhole_lf) return BATCH_OFF_PINHOLE;
+    if (max_depth > rt::kBatchMaxDepth) return BATCH_OFF_DEPTH;
+    if (size_t(static_lds) + p.lds > kTwoBlockLdsBytes || p.blocks_per_cu < 2u) return BATCH_OFF_LDS;
+    if (kernel_blocks >= 0 && uint32_t(kernel_blocks) < p.blocks_per_cu) return BATCH_OFF_OCCUPANCY;
+    return BATCH_ON;
+}
+
 int make_plan(const Inputs& in, const Device& dev, Plan& p, const char** err) {
     if (int rc = plan_form(in, dev, p, err)) return rc;
     const uint64_t tiles_x = (in.band_w + 7u) / 8u, tiles_y = (in.band_h + 7u) / 8u;

@@ -159,6 +159,27 @@ void hand_out_units(const Inputs& in, Plan& p, bool tile_order);
 // on the device for a table planned there.
 uint64_t refill_reserve(const Inputs& in);
 
+// The camera-batch form of the headline kernel (rt_trace_batch.h): whether a launch
+// planned as `p` runs it. Only rt_render_device's launches ask. The form is taken for a HASH launch
+// with the uniform hand-out (table: a block-table launch) that is not instrumented, planned as the
+// one-layer LDS grid walk with shading records (ACCEL_GRID_REC, p.flat), whose camera the host
+// proved pinhole_lf, with max_depth <= kBatchMaxDepth, when the form's own LDS (static_lds of the
+// kernel + the plan's dynamic bytes, rows map included) keeps two blocks per CU and, where the
+// kernels' translation unit was asked (kernel_blocks >= 0), its kernel runs at least the plan's
+// blocks per CU. `tune`: rt_debug_tune's "camera_batches" (0 switches the form off; unset: the
+// default, kCameraBatchesDefault). Returns BATCH_ON or the first reason against, *lds_total the
+// form's static + dynamic LDS bytes.
+enum : uint32_t { BATCH_ON = 0, BATCH_OFF_TUNE = 1, BATCH_OFF_STREAM = 2, BATCH_OFF_TABLE = 3, BATCH_OFF_COUNT = 4,
+                  BATCH_OFF_FORM = 5, BATCH_OFF_PINHOLE = 6, BATCH_OFF_DEPTH = 7, BATCH_OFF_LDS = 8,
+                  BATCH_OFF_OCCUPANCY = 9 };
+constexpr double kCameraBatchesDefault = 1;
+// Static LDS of rt_trace_grid_batch_kernel: the pixel sums, the queue and chain counters, and the
+// walk parameters every walk kernel stages (s_walk_axis, s_walk_slack, s_walk_entry: 104 B, laid out
+// in 112).
+constexpr uint32_t kBatchStaticLdsBytes = rt::kLaneSumLdsBytes + rt::kBatchLdsBytes + 112u;
+uint32_t camera_batches(const Inputs& in, const Plan& p, double tune, uint32_t max_depth, bool table,
+                        uint32_t static_lds, int kernel_blocks, uint32_t* lds_total);
+
 // Both halves for the band of `in` (rt_debug_launch_plan without a context).
 int make_plan(const Inputs& in, const Device& dev, Plan& p, const char** err);
 

@@ -17,6 +17,8 @@ hipError_t launch_trace(const TraceParams& P, uint32_t accel, bool count, int mo
                         hipStream_t st);
 hipError_t trace_occupancy(uint32_t accel, bool count, int mode, bool flat, size_t lds_bytes, int* blocks_per_cu);
 bool flat_grid_form(const TraceParams& P, uint32_t accel, bool count);
+hipError_t launch_trace_batch(const TraceParams& P, int grid, size_t lds_bytes, hipStream_t st);
+hipError_t trace_batch_occupancy(size_t lds_bytes, int* blocks_per_cu, size_t* static_lds);
 uint32_t block_size(uint32_t accel);
 // rt_frame_kernels.hip
 hipError_t launch_resolve_fixed(unsigned long long* fixed, uint64_t n_texels, uint32_t accumulate, uint32_t spp,

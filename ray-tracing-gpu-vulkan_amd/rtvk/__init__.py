@@ -678,15 +678,17 @@ class Renderer:
         """Of the last launch: sample chunks per pixel (of the LPT order's tail ranks; head_chunks:
         of its head ranks, None when there is no head), the kernel form it ran, its dynamic LDS
         bytes, the CU count, whether its grid walk was the one-layer form (flat_grid: the grid is
-        one cell thick in y) and whether its camera rays started at the camera position itself
-        (pinhole_origin) (rt_debug_launch_info)."""
+        one cell thick in y), whether its camera rays started at the camera position itself
+        (pinhole_origin) and whether it ran the camera-batch form of the LDS grid kernel
+        (camera_batches) (rt_debug_launch_info)."""
         v = (ctypes.c_uint32 * 4)()
         check(self._lib.rt_debug_launch_info(self._ctx, v))
         forms = {1: "brute", 2: "lbvh-global", 3: "lbvh-lds", 4: "lbvh-octant-lds", 5: "lbvh-treelet", 6: "grid-lds", 7: "grid-global",
                  8: "grid-lds-coop", 9: "grid-global-coop", 10: "grid-lds-rec", 11: "grid-lds-cq", 12: "grid-lds-rec-cq"}
         return {"chunks": int(v[0]) & 0xffff, "head_chunks": (int(v[0]) >> 16) or None,
                 "form": forms.get(int(v[1]) & 0xffff, str(v[1])), "lds_bytes": int(v[2]), "cus": int(v[3]),
-                "flat_grid": bool((int(v[1]) >> 16) & 1), "pinhole_origin": bool((int(v[1]) >> 17) & 1)}
+                "flat_grid": bool((int(v[1]) >> 16) & 1), "pinhole_origin": bool((int(v[1]) >> 17) & 1),
+                "camera_batches": bool((int(v[1]) >> 18) & 1)}
 
     def launch_plan(self):
         """(abi.LaunchInputs, abi.LaunchPlan) of the last launch (rt_debug_launch_plan): the inputs
@@ -1297,6 +1299,20 @@ def launch_plan(inputs: abi.LaunchInputs) -> abi.LaunchPlan:
     check(load_library().rt_debug_launch_plan(None, ctypes.byref(inputs), ctypes.sizeof(inputs), ctypes.byref(plan),
                                               ctypes.sizeof(plan)))
     return plan
+
+
+CAMERA_BATCH_REASONS = ("on", "tune", "stream", "table", "count", "form", "pinhole", "depth", "lds", "occupancy")
+
+
+def camera_batches(inputs: abi.LaunchInputs, tune: float = -1.0, max_depth: int = 0, table: bool = False,
+                   kernel_blocks: int = -1) -> dict:
+    """Whether rt_render_device runs the camera-batch form for the launch launch_plan(inputs) plans
+    (rt_debug_camera_batches; host only): {"on", "why" (CAMERA_BATCH_REASONS), "static_lds",
+    "lds_total"}."""
+    out = (ctypes.c_uint32 * 3)()
+    check(load_library().rt_debug_camera_batches(ctypes.byref(inputs), ctypes.sizeof(inputs), float(tune), int(max_depth),
+                                                 1 if table else 0, int(kernel_blocks), out))
+    return {"on": out[0] == 0, "why": CAMERA_BATCH_REASONS[out[0]], "static_lds": int(out[1]), "lds_total": int(out[2])}
 
 
 def row_weights(cost, order, tiles_x: int, band_h: int, head_tiles: int = 0, head_chunks: int = 1,

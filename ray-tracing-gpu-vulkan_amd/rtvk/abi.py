@@ -281,6 +281,7 @@ EXPORTS = {
     "rt_debug_exact_exhaustive": (_I, [ctypes.c_int, _P]),
     "rt_debug_launch_info": (_I, [_P, _P]),
     "rt_debug_launch_plan": (_I, [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64]),
+    "rt_debug_camera_batches": (_I, [_P, ctypes.c_uint64, ctypes.c_double, _U32, _U32, _I, ctypes.POINTER(_U32)]),
     "rt_debug_row_weights": (_I, [_P, _P, _U32, _U32, _U32, _U32, _U32, _U32, _P]),
     "rt_debug_kernel_times": (_I, [_P, _P, _U32, ctypes.POINTER(_U32)]),
     "rt_build_info": (ctypes.c_char_p, []),
