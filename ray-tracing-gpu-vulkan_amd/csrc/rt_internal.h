@@ -100,12 +100,32 @@ constexpr unsigned kCoopLdsBytes = (2u * 16u + 8u + 4u) * RT_TRACE_BLOCK;
 // count per wave, a key (u64) per thread.
 constexpr unsigned kCqLdsBytes = (128u * 4u + 4u) * (RT_TRACE_BLOCK / 64u) + 8u * RT_TRACE_BLOCK;
 // Camera-batch form of the LDS grid kernel (rt_trace_batch.h): per wave a queue of kBatchQueue
-// paths (44 B each: o, LCG state, d, pixel | depth, thr) and a chain counter per pixel of its tile,
-// beside the kLaneSumLdsBytes sums (one slot per pixel there). The form reads the winner's records
-// from L2: the static record table does not fit beside the queue in a two-block budget.
+// paths (32 B each: o, LCG state, d, pixel | checker colour | first hit's sphere id; thr is rebuilt
+// from that sphere's material record when the path is popped) and a chain counter per pixel of its
+// tile, beside the kLaneSumLdsBytes sums (one slot per pixel there). The 12 B per entry the thr
+// planes took hold the winner's gate records {cx, cy, cz, r} by sphere id (kBatchGateRecs =
+// kRecStatic of them, 8 192 B) and the camera-origin terms of a generation batch (s_cam_tab, 1 024 B
+// of which 112 are used). The material records still come from L2: the full 48-byte record table
+// does not fit beside the queue in a two-block budget.
+//   24 576 B queue + 3 072 B chain counters + 8 192 B gate table + 1 024 B camera terms = 36 864 B.
+// A/B builds: -DRT_BATCH_GATE_LDS=0 keeps the 44-byte entry and the gate's records in
+// L2, -DRT_BATCH_CAMERA_TERMS=0 the generic ray setup and grid entry in generation batches.
+#ifndef RT_BATCH_GATE_LDS
+#define RT_BATCH_GATE_LDS 1
+#endif
+#ifndef RT_BATCH_CAMERA_TERMS
+#define RT_BATCH_CAMERA_TERMS 1
+#endif
 constexpr unsigned kBatchQueue = 64u;
-constexpr unsigned kBatchLdsBytes = (4u + 16u + 16u + 12u) * RT_TRACE_BLOCK;
-// A queue entry's word holds the path's depth above the pixel's 6 bits.
+constexpr unsigned kBatchGateRecs = 512u;     // == kRecStatic (asserted below)
+constexpr unsigned kBatchCamTabBytes = 1024u;
+#if RT_BATCH_GATE_LDS
+constexpr unsigned kBatchLdsBytes = (4u + 16u + 16u) * RT_TRACE_BLOCK + 16u * kBatchGateRecs + kBatchCamTabBytes;
+#else
+constexpr unsigned kBatchLdsBytes =
+    (4u + 16u + 16u + 12u) * RT_TRACE_BLOCK + (RT_BATCH_CAMERA_TERMS ? kBatchCamTabBytes : 0u);
+#endif
+// The register word of a live lane holds the path's depth above the pixel's 6 bits.
 constexpr uint32_t kBatchMaxDepth = 1u << 26;
 
 // Scene as resident in HBM (one allocation per context, rebuilt by rt_set_scene).
@@ -320,6 +340,7 @@ constexpr uint32_t kFixedFlush = 128;
 // read them through the scalar cache (rt_trace_walk.h setup_ray).
 constexpr uint32_t kBigMax = 64;
 constexpr uint32_t kRecStatic = 512;   // spheres of the REC grid kernels' static LDS record table
+static_assert(kBatchGateRecs == kRecStatic, "the camera-batch form runs where the REC form does: ids below kRecStatic");
 constexpr uint32_t kNoRowsLds = 0xffffffffu;
 constexpr uint32_t kHashMaxSpp = 1u << 19;
 

@@ -381,7 +381,8 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
 
 // Camera-batch form of the LDS grid kernel (rt_trace_batch.h): HASH launches with the uniform
 // hand-out whose plan proved pinhole_lf and a two-block LDS budget (launch_trace_batch's callers). The
-// grid is staged as in rt_trace_grid_kernel; the winner's gate and shading records come from L2
+// grid is staged as in rt_trace_grid_kernel; the winner's gate records and the camera-origin terms
+// are staged in the form's own static LDS (s_gate, s_cam_tab), the shading records come from L2
 // (the static table s_rec does not fit beside the path queue). A kernel of its own, so that every
 // other kernel keeps its name and its code.
 template <bool FLAT>
@@ -399,6 +400,8 @@ __global__ __launch_bounds__(kTraceBlock, RT_TRACE_WAVES_PER_SIMD) void rt_trace
     for (uint32_t i = threadIdx.x; i < nc1; i += kTraceBlock) cst[i] = P.cell_start[i];
     stage_walk_params(P, threadIdx.x);
     stage_rows(P, threadIdx.x, kTraceBlock);
+    stage_gate(P, threadIdx.x, kTraceBlock);
+    stage_camera_terms(P, threadIdx.x);
     __syncthreads();
     batch_loop<FLAT>(P, reinterpret_cast<const float4*>(cst), lds, ids, reinterpret_cast<const float4*>(P.geom),
                      reinterpret_cast<const float4*>(P.mat));

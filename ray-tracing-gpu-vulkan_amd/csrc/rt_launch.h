@@ -173,9 +173,10 @@ enum : uint32_t { BATCH_ON = 0, BATCH_OFF_TUNE = 1, BATCH_OFF_STREAM = 2, BATCH_
                   BATCH_OFF_FORM = 5, BATCH_OFF_PINHOLE = 6, BATCH_OFF_DEPTH = 7, BATCH_OFF_LDS = 8,
                   BATCH_OFF_OCCUPANCY = 9 };
 constexpr double kCameraBatchesDefault = 1;
-// Static LDS of rt_trace_grid_batch_kernel: the pixel sums, the queue and chain counters, and the
+// Static LDS of rt_trace_grid_batch_kernel: the pixel sums (18 432 B), kBatchLdsBytes (36 864 B: the
+// queue, the chain counters, the gate table and the camera-origin terms, rt_internal.h), and the
 // walk parameters every walk kernel stages (s_walk_axis, s_walk_slack, s_walk_entry: 104 B, laid out
-// in 112).
+// in 112): 55 408 B.
 constexpr uint32_t kBatchStaticLdsBytes = rt::kLaneSumLdsBytes + rt::kBatchLdsBytes + 112u;
 uint32_t camera_batches(const Inputs& in, const Plan& p, double tune, uint32_t max_depth, bool table,
                         uint32_t static_lds, int kernel_blocks, uint32_t* lds_total);

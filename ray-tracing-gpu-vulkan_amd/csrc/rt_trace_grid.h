@@ -23,20 +23,27 @@ namespace {
 // coordinate (no accumulated rounding), so the cells visited cover the ray up to rounding distance
 // of the boundaries, which the margin covers. Ties step one axis at a time (an
 // extra cell, never a skipped one).
-template <bool COUNT, bool PAIRS, bool FLAT = false>
+// CAMERA (the camera-batch kernel's generation batches): every ray starts at cam.lf, so the entry
+// box comes as (lo_m - lf, hi_m - lf) from s_cam_tab, the six subtractions done once per block by
+// the same binary32 operation. A lane whose origin is NaN (lens sample (0, 0)) needs no special
+// case: its d and so its inv are NaN, the six products are NaN with either operand, and tn, tf come
+// out as T_MIN and r.limit as they do from (lo - NaN) * NaN (fmaxf / fminf drop a NaN operand,
+// whatever its payload). Everything past the entry test reads r.o itself.
+template <bool COUNT, bool PAIRS, bool FLAT = false, bool CAMERA = false>
 __device__ __forceinline__ void grid_walk(const rt::TraceParams& P, const uint32_t* __restrict__ cstart,
                                           const float4* __restrict__ rec, const uint32_t* __restrict__ ids,
                                           Ray& r, uint32_t& n_cell, uint32_t& n_sph, uint32_t& n_empty) {
     // grid parameters from the block's LDS tables (stage_walk_params), not from the kernel arguments
-    const float4 ex = s_walk_entry[0], ey = s_walk_entry[1], ez = s_walk_entry[2];
+    const float4 ex = CAMERA ? s_cam_tab[4] : s_walk_entry[0], ey = CAMERA ? s_cam_tab[5] : s_walk_entry[1],
+                 ez = CAMERA ? s_cam_tab[6] : s_walk_entry[2];
     const float4 axx = s_walk_axis[0], axy = s_walk_axis[1], axz = s_walk_axis[2];
     const float lo0 = ex.x, lo1 = ey.x, lo2 = ez.x, hi0 = ex.y, hi1 = ey.y, hi2 = ez.y;
     const float ics[3] = {ex.z, ey.z, ez.z}, gmn[3] = {axx.y, axy.y, axz.y}, csz[3] = {axx.x, axy.x, axz.x};
     const int nm1[3] = {int(__float_as_uint(ex.w)), int(__float_as_uint(ey.w)), int(__float_as_uint(ez.w))};
     const uint32_t n0 = __float_as_uint(axx.w), n1 = __float_as_uint(axy.w);
-    const float x0 = (lo0 - r.o.x) * r.inv.x, x1 = (hi0 - r.o.x) * r.inv.x;
-    const float y0 = (lo1 - r.o.y) * r.inv.y, y1 = (hi1 - r.o.y) * r.inv.y;
-    const float z0 = (lo2 - r.o.z) * r.inv.z, z1 = (hi2 - r.o.z) * r.inv.z;
+    const float x0 = (CAMERA ? lo0 : lo0 - r.o.x) * r.inv.x, x1 = (CAMERA ? hi0 : hi0 - r.o.x) * r.inv.x;
+    const float y0 = (CAMERA ? lo1 : lo1 - r.o.y) * r.inv.y, y1 = (CAMERA ? hi1 : hi1 - r.o.y) * r.inv.y;
+    const float z0 = (CAMERA ? lo2 : lo2 - r.o.z) * r.inv.z, z1 = (CAMERA ? hi2 : hi2 - r.o.z) * r.inv.z;
     const float tn = fmaxf(fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1)), T_MIN);
     const float tf = fminf(fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1)), r.limit);
     if (!(tn <= tf)) return;

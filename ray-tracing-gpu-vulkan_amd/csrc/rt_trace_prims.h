@@ -102,6 +102,15 @@ __device__ __forceinline__ void stage_walk_params(const rt::TraceParams& P, uint
     if (tid == 3u) s_walk_slack = make_float2(P.cull_near_abs, P.cull_abs);
 }
 
+// The camera-batch kernel's camera-origin terms (rt_trace_batch.h stage_camera_terms, its only
+// writer; read by setup_ray<.., CAMERA> and grid_walk<.., CAMERA>): every camera ray of a pinhole_lf
+// launch starts at cam.lf, so what a segment's setup computes from the origin alone is the same for
+// every generation batch of the frame.
+//   [0..3] {oc.x, oc.y, oc.z, c} of the first four big spheres: oc = lf - centre, c = |oc|^2 - r^2
+//   [4..6] per axis the grid's entry box from lf: (lo_m - lf, hi_m - lf, inv_cs, n - 1 as uint bits)
+// The rest of its 1 KB is spare (rt_internal.h kBatchCamTabBytes).
+__shared__ float4 s_cam_tab[rt::kBatchCamTabBytes / 16u];
+
 // One DDA step of the grid walks: the axis whose boundary comes first (x before y before z on
 // ties; tm = the smallest boundary t). Only the stepped coordinate can leave the grid (false:
 // the ray left). The new boundary's t is recomputed from the cell coordinate, never accumulated.

@@ -150,9 +150,12 @@ __device__ __forceinline__ HitRec load_hit_rec(uint32_t bi) {
 // the next ray), false when its unit's samples are done.
 // hr: the records of sphere bi (load_hit), loaded by the caller so that they can travel with the
 // winner gate's loads (lbvh_loop); unused on a miss.
-template <int MODE, bool LSUM, bool FAST = false>
+// ALT (the camera-batch kernel's generation batches): *alt is set to 1 where the checker texture
+// chose colour 1 (the caller clears it), so the caller knows which material record att came from.
+template <int MODE, bool LSUM, bool FAST = false, bool ALT = false>
 __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera& cam, const HitRec& hr, Path& ps,
-                                          uint32_t bi, float best, V3& o, V3& d, bool& fresh) {
+                                          uint32_t bi, float best, V3& o, V3& d, bool& fresh,
+                                          uint32_t* alt = nullptr) {
     if constexpr (MODE == rt::MODE_PROBE) {   // the closest hit is the answer: no shading, the unit ends
         const size_t i = size_t(ps.px >> 16) * P.band_w + (ps.px & 0xffffu);
         P.probe_out[2 * i] = bi;
@@ -210,7 +213,10 @@ __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera
         const V3 n = front ? outward : neg(outward);
         // shader.rchit:53-64
         att = v3(m0.x, m0.y, m0.z);
-        if (ttype == 1u && !checker_positive(p.x, p.y, p.z)) att = v3(m1.x, m1.y, m1.z);
+        if (ttype == 1u && !checker_positive(p.x, p.y, p.z)) {
+            att = v3(m1.x, m1.y, m1.z);
+            if constexpr (ALT) *alt = 1u;
+        }
         // diffuse and metal both draw one random unit vector first (shader.rchit:69, :80): one
         // copy of that code serves a wave holding both materials
         V3 ru = v3(0.0f, 0.0f, 0.0f);

@@ -117,8 +117,39 @@ __device__ __forceinline__ void big_group(Ray& r, const float (&sb)[16], const u
     }
 }
 
+// big_group for the camera-batch kernel's generation batches: the rays start at cam.lf, so oc and c
+// of the four spheres come from s_cam_tab (stage_camera_terms: big_group's own expressions on lf,
+// once per block) instead of seven VALU per sphere and lane; b, D and the candidate tails are
+// big_group's. A lane whose origin is NaN (lens sample (0, 0)) needs no special case: its d is NaN,
+// so b and D are NaN with either oc, D >= 0 is false and the lane has no candidate, as now.
+__device__ __forceinline__ void big_group_camera(Ray& r, const uint32_t (&ib)[4]) {
+    float bk[4], Dk[4];
+    uint32_t cand = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 q = s_cam_tab[k];   // {oc.x, oc.y, oc.z, c}: one wave-uniform ds_read_b128
+        bk[k] = __builtin_fmaf(q.z, r.d.z, __builtin_fmaf(q.y, r.d.y, q.x * r.d.x));
+        Dk[k] = __builtin_fmaf(bk[k], bk[k], -(r.a * q.w));
+        cand |= (Dk[k] >= 0.0f && !behind(bk[k], q.w) ? 1u : 0u) << k;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if ((cand >> k) & 1u) {
+            const float sq = sqrt_cr(Dk[k]);
+            float t = (-bk[k] - sq) * r.ia;
+            if (!(t >= T_MIN)) t = (-bk[k] + sq) * r.ia;   // report t1 if t1 >= tmin, else t2
+            const uint32_t id = ib[k];
+            if ((t >= T_MIN) & (t <= r.best) & ((t < r.best) | (id < r.bi))) {
+                r.best = t;
+                r.bi = id;
+            }
+        }
+    }
+}
+
 // New segment: hoisted per-ray terms and the exhaustive big spheres.
-template <bool FAST = false>   // FAST: at most 4 big spheres (the one-layer L2 grid kernel, lbvh_loop SPEC)
+// CAMERA: a generation batch of the camera-batch kernel (big_group_camera).
+template <bool FAST = false, bool CAMERA = false>   // FAST: at most 4 big spheres (the one-layer L2 grid kernel, lbvh_loop SPEC)
 __device__ __forceinline__ void setup_ray(const rt::TraceParams& P, Ray& r) {
     // records and ids through the scalar cache (TraceParams::big_tab, SGPR operands, no LDS round
     // trip: config 3 -1.6 %, reference stream -1.7 %, config 5 -2.2 % against an LDS table); the
@@ -133,8 +164,10 @@ __device__ __forceinline__ void setup_ray(const rt::TraceParams& P, Ray& r) {
     // safe whatever n_big); the ids come with the records, not one dependent load per candidate
     float sb0[16];
     uint32_t ib0[4];
+    if constexpr (!CAMERA) {
 #pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) sb0[k] = g[k];
+        for (uint32_t k = 0; k < 16; ++k) sb0[k] = g[k];
+    }
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) ib0[k] = gid[k];
     r.a = dot(r.d, r.d);
@@ -145,7 +178,8 @@ __device__ __forceinline__ void setup_ray(const rt::TraceParams& P, Ray& r) {
     // beyond it, and the (t bits, id) keys of the cooperative walk order the same way.
     r.best = 10000.0f;
     r.bi = 0xffffffffu;
-    big_group(r, sb0, ib0);   // (without big spheres the table holds four inert records: no test)
+    if constexpr (CAMERA) big_group_camera(r, ib0);
+    else big_group(r, sb0, ib0);   // (without big spheres the table holds four inert records: no test)
     for (uint32_t k0 = 4; !FAST && k0 < P.n_big; k0 += 4) {
         float sb[16];
         uint32_t ib[4];
@@ -259,7 +293,7 @@ __device__ __forceinline__ void regate_brute(const rt::TraceParams& P, const flo
 }
 
 // The whole walk of one segment. FLAT: the grid is one cell thick in y (grid_walk).
-template <bool COUNT, int LAYOUT, bool FLAT = false>
+template <bool COUNT, int LAYOUT, bool FLAT = false, bool CAMERA = false>
 __device__ __forceinline__ void walk(const rt::TraceParams& P, const float4* __restrict__ nodes4,
                                      const float4* __restrict__ leaf4, const uint32_t* __restrict__ leaf_ids,
                                      Ray& r, uint32_t& n_box, uint32_t& n_sph, uint32_t& n_empty) {
@@ -270,7 +304,7 @@ __device__ __forceinline__ void walk(const rt::TraceParams& P, const float4* __r
     }
     if (LAYOUT == LAYOUT_GRID || LAYOUT == LAYOUT_GRID_L2) {   // nodes4 = cell offsets, leaf4 / leaf_ids = references
         if (r.walk)
-            grid_walk<COUNT, LAYOUT == LAYOUT_GRID_L2, FLAT>(P, reinterpret_cast<const uint32_t*>(nodes4), leaf4, leaf_ids,
+            grid_walk<COUNT, LAYOUT == LAYOUT_GRID_L2, FLAT, CAMERA>(P, reinterpret_cast<const uint32_t*>(nodes4), leaf4, leaf_ids,
                                                              r, n_box, n_sph, n_empty);
         return;
     }
