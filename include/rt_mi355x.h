@@ -407,6 +407,56 @@ int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* 
                                          uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
                                          rt_sample_map* map, const rt_sample_map_feedback* fb,
                                          uint64_t* d_tile_error, void* stream);
+/*
+ * The hand-over of the two halves. Adaptive and feedback frames sum the first
+ * half of every tile's samples into fixed-point planes A and the second into planes B; the two calls
+ * below are rt_render_adaptive_device and rt_render_sample_map_feedback_device with one more
+ * argument, and their resolve (the same single pass over the planes) also writes the halves, in the
+ * form the variance-guided filter and the temporal stage read a frame. With qA, qB the per-channel
+ * 8.24 integers the plane sets hold when the frame resolves and n the texel's tile count (even in
+ * both frame kinds), per band texel in band order (a row map is honoured exactly as for accum):
+ *   accum_a    = (float(double(qA.r) * 2^-24), float(double(qA.g) * 2^-24), float(double(qA.b) * 2^-24), 1)
+ *   accum_b    likewise from qB
+ *   half_count = n / 2
+ *   accum_rgba32f, out_rgba8, sample_count, info and d_tile_error exactly as the calls without
+ *   halves write them, from qA + qB.
+ * What the halves hold:
+ *   Feedback frame. A tile of count n = 2 h at sample_base = b has A = samples [b, b + h) and B =
+ *     [b + h, b + n): accum_a equals rt_render_device at samplesPerRenderCall = h, sample_base = b in
+ *     every texel of the tile, bit for bit, and accum_b the same call at sample_base = b + h (the
+ *     uniform frame's resolve is the same float(double(q) * 2^-24)). A tile of count 0 gives
+ *     (0, 0, 0, 1) twice and h = 0.
+ *   Adaptive frame. A tile that ran passes of k_0 = min_spp, k_1, ... samples starting at d_0 = 0,
+ *     d_1 = k_0, ... has A = the samples of the union over j of [b + d_j, b + d_j + k_j / 2) and B =
+ *     the rest of [b, b + n); h = n / 2.
+ * RT_ERR_INVALID_ARGUMENT before anything is queued (rt_last_error() names the field), beside the
+ * refusals of the calls without halves: halves NULL, accum_a or accum_b NULL, reserved not NULL,
+ * accum_a == accum_b, either equal to accum_rgba32f. rt_half_outputs_check is these checks alone
+ * (host only, no device and no context needed). Everything else is the plain calls': synchronisation,
+ * launch records, what they leave in the context (the planes are zero afterwards); a feedback halves
+ * frame still contains no host wait.
+ * The planes feed the filters unchanged: rt_denoise_variance_device(accum_a, accum_b, half_count, ...)
+ * and rt_temporal_accumulate_device / rt_temporal_reproject_device(accum_a, accum_b, sample_count =
+ * half_count, ...), see there.
+ */
+typedef struct rt_half_outputs {
+    float*    accum_a;     /* DEVICE float4 per band texel: (sum of the A half, 1)    */
+    float*    accum_b;     /* DEVICE float4 per band texel: (sum of the B half, 1)    */
+    uint32_t* half_count;  /* optional DEVICE uint32 per band texel: h = n[tile] / 2  */
+    void*     reserved;    /* NULL */
+} rt_half_outputs;
+int rt_half_outputs_check(const rt_half_outputs* halves, const float* accum_rgba32f);
+int rt_render_adaptive_halves_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                     uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
+                                     uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
+                                     const rt_adaptive* ad, rt_adaptive_info* info,
+                                     const rt_half_outputs* halves, void* stream);
+int rt_render_sample_map_feedback_halves_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                                uint32_t band_width, uint32_t band_height, float* accum_rgba32f,
+                                                uint8_t* out_rgba8, uint32_t* sample_count, const rt_options* opt,
+                                                rt_sample_map* map, const rt_sample_map_feedback* fb,
+                                                uint64_t* d_tile_error, const rt_half_outputs* halves,
+                                                void* stream);
 /* Statistics of the last completed rt_render_device (synchronises ctx's last stream). */
 int rt_get_stats(rt_context* ctx, rt_stats* out);
 /* Trace-kernel duration (ms, HIP events on the launch stream) of ctx's launch `back` launches
@@ -525,7 +575,9 @@ int rt_denoise_device(rt_context* ctx, const float* accum_rgba32f, const uint32_
  * rt_render_device calls with samplesPerRenderCall = h under RT_RNG_SAMPLE_HASH, one at
  * sample_base = b and one at sample_base = b + h; a sample-map frame is two
  * rt_render_sample_map_device frames whose sample_base differ by the cap, and half_count is the
- * sample_count plane either writes. Every operation is one correctly rounded binary32 + - x /, in
+ * sample_count plane either writes; an adaptive or feedback frame rendered once hands its own two
+ * halves over (rt_half_outputs above): rt_denoise_variance_device(accum_a, accum_b, half_count, ...),
+ * a texel of h = 0 has ma = mb = 0. Every operation is one correctly rounded binary32 + - x /, in
  * this order (tests/denoise_var_sim.py gives the same bits); taps, their order and the borders are
  * rt_denoise_device's, K = {3/8, 1/4, 1/16}:
  *     hf = float(h_p);  ma = h_p ? A.rgb / hf : 0;  mb = h_p ? B.rgb / hf : 0
@@ -606,6 +658,9 @@ int rt_denoise_variance_device(rt_context* ctx, const float* accum_a, const floa
  *                     each; accum_b optional: NULL is one accumulator, HB is then neither read nor
  *                     written and out_b must be NULL too (and the reverse).
  *   sample_count      optional DEVICE array of uint32 per texel; NULL: every texel has `spp` samples.
+ *                     The halves of an adaptive or feedback frame (rt_half_outputs above) go in as
+ *                     (accum_a, accum_b, sample_count = half_count), here and in
+ *                     rt_temporal_reproject_device; the frames' sample_base advances by the cap.
  *   feat0, feat1, feature_samples   as rt_render_features_device wrote them.
  *   params            NULL: {8, 4.0f, 16.0f, 0}.
  *   out_a, out_b      DEVICE float4 arrays; out_rgba8 (4 bytes per texel) and history_len (uint32 per

@@ -238,6 +238,14 @@ int rt_debug_multi_balance_info(const rt_multi* m, double* out4);
  * step <= max_step stage their taps in LDS, the others read them from global memory. 0 (every
  * iteration from global memory), 1, 2 or 4 (the default); other values: RT_ERR_INVALID_ARGUMENT. */
 int rt_debug_denoise_lds_steps(rt_context* ctx, uint32_t max_step);
+/* Timing: the resolve of adaptive and feedback frames alone, one launch on `stream`, over the context's
+ * fixed-point planes as they stand (zero between frames, and zero again afterwards) with `count` as
+ * every tile's count. halves NULL: the plain resolve; else rt_half_outputs' rules and the resolve that
+ * also hands the halves over. The outputs are band_width x band_height texels, sample_count optional.
+ * Forgets the count table of the last adaptive frame. Refused while an adaptive frame is open. */
+int rt_debug_adaptive_resolve(rt_context* ctx, uint32_t band_width, uint32_t band_height, uint32_t count,
+                              float* accum_rgba32f, uint8_t* out_rgba8, uint32_t* sample_count,
+                              const rt_half_outputs* halves, void* stream);
 
 #ifdef __cplusplus
 }  /* extern "C" */

@@ -130,6 +130,38 @@ __global__ __launch_bounds__(256) void rt_adaptive_resolve_kernel(unsigned long 
     }
 }
 
+// rt_adaptive_resolve_kernel with the hand-over of the two halves (rt_render_adaptive_halves_device,
+// rt_render_sample_map_feedback_halves_device): the same single pass over the
+// planes also stores A and B, each resolved as the sum is (an exact product, one rounding), and the
+// optional per-texel half count cnt / 2. 156 B per texel instead of 120 B; every float4 is one
+// 16-byte store per lane, the plane loads stay 8-byte and wave-contiguous. A sibling and not a
+// template of the kernel above: that one's listing stays the parent's (scripts/isa_same.py).
+__global__ __launch_bounds__(256) void rt_adaptive_resolve_halves_kernel(
+    unsigned long long* __restrict__ a, unsigned long long* __restrict__ b, uint64_t n, uint32_t band_w,
+    uint32_t tiles_x, const uint32_t* __restrict__ tile_n, float4* __restrict__ accum, uint32_t* __restrict__ out,
+    uint32_t* __restrict__ sample_count, float4* __restrict__ accum_a, float4* __restrict__ accum_b,
+    uint32_t* __restrict__ half_count) {
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t y = uint32_t(i) / band_w, x = uint32_t(i) - y * band_w;   // n < 2^32 (band sides < 2^16)
+        const uint32_t cnt = tile_n[(y >> 3) * tiles_x + (x >> 3)];
+        const unsigned long long a0 = a[i], a1 = a[n + i], a2 = a[2 * n + i];
+        const unsigned long long b0 = b[i], b1 = b[n + i], b2 = b[2 * n + i];
+        a[i] = 0ull; a[n + i] = 0ull; a[2 * n + i] = 0ull;
+        b[i] = 0ull; b[n + i] = 0ull; b[2 * n + i] = 0ull;
+        accum_a[i] = make_float4(float(double(a0) * 0x1p-24), float(double(a1) * 0x1p-24), float(double(a2) * 0x1p-24), 1.0f);
+        accum_b[i] = make_float4(float(double(b0) * 0x1p-24), float(double(b1) * 0x1p-24), float(double(b2) * 0x1p-24), 1.0f);
+        const float s0 = float(double(a0 + b0) * 0x1p-24);
+        const float s1 = float(double(a1 + b1) * 0x1p-24);
+        const float s2 = float(double(a2 + b2) * 0x1p-24);
+        accum[i] = make_float4(s0, s1, s2, 1.0f);
+        const float spp = float(cnt);
+        out[i] = unorm8(__builtin_sqrtf(s0 / spp)) | (unorm8(__builtin_sqrtf(s1 / spp)) << 8) |
+                 (unorm8(__builtin_sqrtf(s2 / spp)) << 16) | (255u << 24);
+        if (sample_count) sample_count[i] = cnt;
+        if (half_count) half_count[i] = cnt >> 1;
+    }
+}
+
 // The store of a multi-device adaptive frame (rt_multi_render_adaptive), on device 0, once per part:
 // band row y of `src` (the part's resolved float4 sums, n_rows x width) goes to image row rows[y]
 // of the accumulator, the rgba8 image and the optional count map, tonemapped with the count of the
@@ -190,11 +222,17 @@ hipError_t launch_feedback_update(const FeedbackParams& K, hipStream_t st) {
 
 hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
                                    uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
-                                   uint32_t* sample_count, hipStream_t st) {
+                                   uint32_t* sample_count, float* accum_a, float* accum_b, uint32_t* half_count,
+                                   hipStream_t st) {
     const uint64_t need = (n_texels + 255) / 256;
-    hipLaunchKernelGGL(rt_adaptive_resolve_kernel, dim3(uint32_t(need < 8192 ? need : 8192)), dim3(256), 0, st, a, b,
-                       n_texels, band_w, tiles_x, tile_n, reinterpret_cast<float4*>(accum),
-                       reinterpret_cast<uint32_t*>(out), sample_count);
+    const dim3 grid(uint32_t(need < 8192 ? need : 8192));
+    if (accum_a)
+        hipLaunchKernelGGL(rt_adaptive_resolve_halves_kernel, grid, dim3(256), 0, st, a, b, n_texels, band_w, tiles_x,
+                           tile_n, reinterpret_cast<float4*>(accum), reinterpret_cast<uint32_t*>(out), sample_count,
+                           reinterpret_cast<float4*>(accum_a), reinterpret_cast<float4*>(accum_b), half_count);
+    else
+        hipLaunchKernelGGL(rt_adaptive_resolve_kernel, grid, dim3(256), 0, st, a, b, n_texels, band_w, tiles_x, tile_n,
+                           reinterpret_cast<float4*>(accum), reinterpret_cast<uint32_t*>(out), sample_count);
     return hipGetLastError();
 }
 

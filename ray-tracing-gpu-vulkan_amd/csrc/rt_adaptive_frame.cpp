@@ -216,7 +216,20 @@ int adaptive_pass_done(rt_context* ctx, bool block, bool* done) {
     return RT_OK;
 }
 
-int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info) {
+int half_outputs_check(const rt_half_outputs* halves, const float* accum) {
+    if (!halves) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: halves is NULL");
+    if (!halves->accum_a) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: accum_a is NULL");
+    if (!halves->accum_b) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: accum_b is NULL");
+    if (halves->reserved) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: reserved must be NULL");
+    if (halves->accum_a == halves->accum_b)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: accum_a and accum_b are the same array");
+    if (halves->accum_a == accum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: accum_a is accum_rgba32f");
+    if (halves->accum_b == accum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_half_outputs: accum_b is accum_rgba32f");
+    return RT_OK;
+}
+
+int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info,
+                    const rt_half_outputs* halves) {
     rt_context::Adaptive& a = ctx->adaptive;
     rt_context::Adaptive::Frame& f = a.frame;
     if (!f.open || f.pending || f.active) return fail(RT_ERR_INVALID_ARGUMENT, "adaptive finish out of order");
@@ -224,7 +237,9 @@ int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sampl
     const AdaptiveBuffers b = adaptive_buffers(ctx);
     const rt::TraceParams& P = f.S.P;
     if (hipError_t e = rt::launch_adaptive_resolve(b.half[0], b.half[1], b.texels, P.band_w, P.tiles_x, b.tile_n, accum,
-                                                   out, sample_count, f.st);
+                                                   out, sample_count, halves ? halves->accum_a : nullptr,
+                                                   halves ? halves->accum_b : nullptr,
+                                                   halves ? halves->half_count : nullptr, f.st);
         e != hipSuccess)
         return adaptive_abort(ctx, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
     if (info) {
@@ -257,17 +272,16 @@ int adaptive_store_tiles(int device, const float* src, uint32_t n_rows, uint32_t
 
 using rt::fail;
 
-extern "C" {
+namespace {
 
-int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
-                              uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
-                              uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
-                              rt_adaptive_info* info, void* stream) {
-    if (info) std::memset(info, 0, sizeof(*info));
+// rt_render_adaptive_device (halves null) and rt_render_adaptive_halves_device (halves checked).
+int render_adaptive(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                    uint32_t band_height, float* accum, uint8_t* out, uint32_t* sample_count, const rt_options* opt,
+                    const rt_adaptive* ad, rt_adaptive_info* info, const rt_half_outputs* halves, void* stream,
+                    const char* who) {
     // the state machine of rt_host.h, one context: each pass waits for its own readback
     bool open = false;
-    if (int rc = rt::adaptive_begin(ctx, rci, rows, band_width, band_height, accum, out, opt, ad, stream,
-                                    "rt_render_adaptive_device", &open))
+    if (int rc = rt::adaptive_begin(ctx, rci, rows, band_width, band_height, accum, out, opt, ad, stream, who, &open))
         return rc;
     if (!open) return RT_OK;   // a band without texels
     int rc = RT_OK;
@@ -276,7 +290,58 @@ int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const 
         if (rc == RT_OK) rc = rt::adaptive_pass_done(ctx, true, nullptr);
     }
     if (rc != RT_OK) return rt::adaptive_abort(ctx, rc);
-    return rt::adaptive_finish(ctx, accum, out, sample_count, info);
+    return rt::adaptive_finish(ctx, accum, out, sample_count, info, halves);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_adaptive_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                              uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                              uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
+                              rt_adaptive_info* info, void* stream) {
+    if (info) std::memset(info, 0, sizeof(*info));
+    return render_adaptive(ctx, rci, rows, band_width, band_height, accum, out, sample_count, opt, ad, info, nullptr,
+                           stream, "rt_render_adaptive_device");
+}
+
+int rt_half_outputs_check(const rt_half_outputs* halves, const float* accum) {
+    return rt::half_outputs_check(halves, accum);
+}
+
+int rt_render_adaptive_halves_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                     uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                                     uint32_t* sample_count, const rt_options* opt, const rt_adaptive* ad,
+                                     rt_adaptive_info* info, const rt_half_outputs* halves, void* stream) {
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (int rc = rt::half_outputs_check(halves, accum)) return rc;
+    return render_adaptive(ctx, rci, rows, band_width, band_height, accum, out, sample_count, opt, ad, info, halves,
+                           stream, "rt_render_adaptive_halves_device");
+}
+
+int rt_debug_adaptive_resolve(rt_context* ctx, uint32_t band_width, uint32_t band_height, uint32_t count, float* accum,
+                              uint8_t* out, uint32_t* sample_count, const rt_half_outputs* halves, void* stream) {
+    if (!ctx || !accum || !out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_resolve: ctx, accum or out is NULL");
+    if (band_width == 0 || band_height == 0 || band_width > 65535u || band_height > 65535u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_resolve: band width and height must be within 1 .. 65535");
+    if (halves)
+        if (int rc = rt::half_outputs_check(halves, accum)) return rc;
+    rt_context::Adaptive& a = ctx->adaptive;
+    if (a.frame.open) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_resolve: an adaptive frame is open on this context");
+    rt::DeviceGuard g(ctx->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = rt::order_on(ctx, st)) return rc;
+    const uint64_t texels = uint64_t(band_width) * band_height;
+    const uint32_t tiles_x = (band_width + 7u) / 8u;
+    const uint64_t n_tiles = uint64_t(tiles_x) * ((band_height + 7u) / 8u);
+    if (int rc = rt::adaptive_reserve(ctx, texels, n_tiles, st)) return rc;
+    a.last_w = a.last_h = 0;   // the count table below replaces the last frame's
+    RT_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.tiles), int(count), n_tiles, st));
+    RT_HIP(rt::launch_adaptive_resolve(a.planes, a.planes + 3u * texels, texels, band_width, tiles_x, a.tiles, accum, out,
+                                       sample_count, halves ? halves->accum_a : nullptr,
+                                       halves ? halves->accum_b : nullptr, halves ? halves->half_count : nullptr, st));
+    return rt::mark_issued(ctx, st);
 }
 
 int rt_adaptive_tile_converged(uint64_t E, uint64_t S, uint32_t n, uint32_t m, uint32_t thr_q16, int* converged) {

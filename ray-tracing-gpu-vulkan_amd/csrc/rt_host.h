@@ -51,7 +51,8 @@ void keep_row_weights(rt_context* ctx);
 //   adaptive_pass_done   has that readback landed? block = false: hipEventQuery (*done = false
 //                   when not yet); block = true waits. Consumes it once landed: the next pass's list.
 //   adaptive_finish the resolve into accum / out / sample_count (band layout; sample_count optional),
-//                   fills info (optional) and closes the frame.
+//                   fills info (optional) and closes the frame. halves (optional, checked by the
+//                   caller): the same resolve also writes the two halves and the half counts.
 //   adaptive_abort  after a failed step: clears the half-buffers (A and B are zero between calls,
 //                   whatever happened) and closes the frame; returns rc (or the closing's own error).
 //   adaptive_tile_counts  DEVICE pointer of the band's per-tile sample counts (ceil(W / 8) x
@@ -67,7 +68,11 @@ int adaptive_begin(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* r
 bool adaptive_active(const rt_context* ctx);
 int adaptive_issue_pass(rt_context* ctx);
 int adaptive_pass_done(rt_context* ctx, bool block, bool* done);
-int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info);
+int adaptive_finish(rt_context* ctx, float* accum, uint8_t* out, uint32_t* sample_count, rt_adaptive_info* info,
+                    const rt_half_outputs* halves = nullptr);
+// The host-only refusals of a halves frame (rt_half_outputs_check): a NULL struct or accumulator, a
+// non-NULL reserved, accum_a == accum_b, either equal to `accum`.
+int half_outputs_check(const rt_half_outputs* halves, const float* accum);
 int adaptive_abort(rt_context* ctx, int rc);
 const uint32_t* adaptive_tile_counts(const rt_context* ctx);
 // The fused store of a multi-device adaptive frame on `device` (rt_adaptive.hip

@@ -39,9 +39,11 @@ hipError_t launch_scatter_probe(const ScatterProbeParams& K, bool rec, hipStream
 // rt_adaptive.hip
 hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st);
 hipError_t launch_adaptive_error(const AdaptiveErrorParams& K, hipStream_t st);
+// (accum_a non-null: the resolve that also hands the two halves over; accum_b then too, half_count optional)
 hipError_t launch_adaptive_resolve(unsigned long long* a, unsigned long long* b, uint64_t n_texels, uint32_t band_w,
                                    uint32_t tiles_x, const uint32_t* tile_n, float* accum, uint8_t* out,
-                                   uint32_t* sample_count, hipStream_t st);
+                                   uint32_t* sample_count, float* accum_a, float* accum_b, uint32_t* half_count,
+                                   hipStream_t st);
 hipError_t launch_feedback_update(const FeedbackParams& K, hipStream_t st);
 hipError_t launch_adaptive_store_tiles(const float* src, uint32_t n_rows, uint32_t width, const uint32_t* tile_n,
                                        const uint32_t* rows, uint32_t dst_rows, float* accum, uint8_t* out,

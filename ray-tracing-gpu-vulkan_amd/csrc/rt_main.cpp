@@ -49,6 +49,17 @@
 //   --camera-step S: frame k's camera stands at (13 + S k, 11, -3 + 2 S k) and looks at the origin
 //   (default 0: the reference's camera every frame), with or without --reproject. Refused without
 //   --temporal.
+//   --adaptive T[,MIN[,STEP]] --samples CAP --frames K --feedback --denoise-variance [F[,ITER[,PRE]]]
+//   [--temporal [N] [--reproject] [--camera-step S]] [--animate]: the feedback loop through the filters,
+//   the one pairing of noise-driven frames with them. Frame 0 is an adaptive frame and every later frame
+//   a feedback frame (min, max, cap and threshold as --feedback derives them), frame k from sample_base
+//   k x CAP; each hands its two halves and half counts over (rt_render_adaptive_halves_device,
+//   rt_render_sample_map_feedback_halves_device), then the features at sample_base 0, with --reproject
+//   the motion pass, with --temporal the stage on the two halves (sample_count = the half counts), and
+//   the variance-guided filter (on the stage's outputs at half_spp 1, else on the halves with their
+//   counts), all on one stream; --store writes the last frame's filtered image. Refused when K x CAP
+//   does not fit 32 bits. Without --feedback, --denoise-variance and --temporal still refuse --adaptive,
+//   and --denoise (the plain filter) refuses --frames as before.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -550,6 +561,147 @@ int run_temporal_frames(uint32_t samples, uint32_t width, uint32_t height, uint3
     return 0;
 }
 
+// The feedback loop through the filters, on device 0 (--adaptive --frames --feedback --denoise-variance,
+// optionally --temporal [--reproject] [--camera-step]): frame 0 is an adaptive halves frame and every
+// later frame a feedback halves frame, with the feedback parameters run_adaptive_frames derives; frame k
+// renders from sample_base k x samples (the cap), so the frames' noise is independent. Every frame hands
+// its two halves and half counts over (rt_half_outputs); then the features at sample_base 0, with tp
+// the temporal stage on the halves (reprojected behind the motion pass, or in place) and the
+// variance-guided filter: on the stage's outputs at half_spp 1, or on the halves with their counts.
+// Everything on one stream; after the one set call behind frame 0 nothing waits but a window's end.
+int run_feedback_filtered_frames(uint32_t samples, uint32_t width, uint32_t height, uint32_t frames, bool animate,
+                                 bool store, const rt_adaptive& ad, uint32_t feature_samples,
+                                 const rt_denoise_variance& dv, const rt_temporal_params* tp, bool reproject,
+                                 float camera_step) {
+    rt_context* ctx = nullptr;
+    rt_sample_map* map = nullptr;
+    rt_temporal* temporal = nullptr;
+    rt_motion* motion = nullptr;
+    hipStream_t stream = nullptr;
+    float *accum = nullptr, *accum_a = nullptr, *accum_b = nullptr, *feat0 = nullptr, *feat1 = nullptr;
+    float *out_a = nullptr, *out_b = nullptr, *motion_plane = nullptr;
+    uint32_t* half_count = nullptr;
+    uint8_t* rgba8 = nullptr;
+    const size_t texels = size_t(width) * height;
+    CLI_HIP(hipSetDevice(0));
+    CLI_RT(rt_context_create(0, &ctx));
+    CLI_RT(rt_sample_map_create(ctx, width, height, &map));
+    CLI_RT(rt_sample_map_set_schedule(map, RT_SAMPLE_MAP_ONE_LAUNCH, 0));
+    CLI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    for (float** p : {&accum, &accum_a, &accum_b, &feat0, &feat1}) CLI_HIP(hipMalloc(p, texels * 16));
+    CLI_HIP(hipMalloc(&half_count, texels * 4));
+    CLI_HIP(hipMalloc(&rgba8, texels * 4));
+    if (tp) {
+        CLI_RT(rt_temporal_create(ctx, width, height, &temporal));
+        CLI_HIP(hipMalloc(&out_a, texels * 16));
+        CLI_HIP(hipMalloc(&out_b, texels * 16));
+    }
+    if (reproject) {
+        CLI_RT(rt_motion_create(ctx, width, height, &motion));
+        CLI_HIP(hipMalloc(&motion_plane, texels * 16));
+    }
+    const rt_half_outputs halves = {accum_a, accum_b, half_count, nullptr};
+    rt_options feat_opt;
+    std::memset(&feat_opt, 0, sizeof(feat_opt));
+    feat_opt.rng_mode = RT_RNG_SAMPLE_HASH;
+    rt_sample_map_feedback fb;
+    std::memset(&fb, 0, sizeof(fb));
+    fb.threshold = ad.threshold;
+    fb.min_spp = ad.min_spp;
+    fb.max_spp = samples;
+    rt_sample_map_info map_info;
+    std::memset(&map_info, 0, sizeof(map_info));
+    std::vector<Sphere> scene(488);
+    uint32_t cnt = 0, frame_index = 0, window_feedback = 0;
+    bool map_stale = true;   // an adaptive frame has run since the map was set
+    const auto t_start = std::chrono::steady_clock::now();
+    auto frame = [&]() -> int {
+        const float t = animate ? std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count() : 0.0f;
+        CLI_RT(rt_generate_scene(t, 11, scene.data(), uint32_t(scene.size()), &cnt));
+        CLI_RT(rt_set_scene(ctx, scene.data(), cnt, stream));
+        RenderCallInfo rci;
+        CLI_RT(rt_canonical_render_call_info(samples, width, height, &rci));
+        if (camera_step != 0.0f) {   // frame k of the path; it looks at the origin
+            rci.camera_pos.x = 13.0f + camera_step * float(frame_index);
+            rci.camera_pos.z = -3.0f + (2.0f * camera_step) * float(frame_index);
+            rci.camera_dir = rt_vec4{-rci.camera_pos.x, -rci.camera_pos.y, -rci.camera_pos.z, 0.0f};
+        }
+        rt_options opt = feat_opt;
+        opt.sample_base = frame_index * samples;
+        if (frame_index == 0) {
+            rt_adaptive_info info;
+            CLI_RT(rt_render_adaptive_halves_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt, &ad, &info,
+                                                    &halves, stream));
+            map_stale = true;
+        } else {
+            if (map_stale) CLI_RT(rt_sample_map_set_from_adaptive(map, 0, stream, &map_info));
+            map_stale = false;
+            CLI_RT(rt_render_sample_map_feedback_halves_device(ctx, &rci, nullptr, width, height, accum, rgba8, nullptr, &opt,
+                                                               map, &fb, nullptr, &halves, stream));
+            ++window_feedback;
+        }
+        CLI_RT(rt_render_features_device(ctx, &rci, nullptr, width, height, feat0, feat1, feature_samples, &feat_opt, stream));
+        if (reproject) {
+            CLI_RT(rt_render_motion_device(ctx, motion, &rci, motion_plane, nullptr, stream));
+            CLI_RT(rt_motion_keep_current(ctx, motion, &rci, stream));
+            CLI_RT(rt_temporal_reproject_device(ctx, temporal, accum_a, accum_b, half_count, 0, feat0, feat1, feature_samples,
+                                                motion_plane, tp, out_a, out_b, nullptr, nullptr, stream));
+        } else if (tp) {
+            CLI_RT(rt_temporal_accumulate_device(ctx, temporal, accum_a, accum_b, half_count, 0, feat0, feat1, feature_samples,
+                                                 tp, out_a, out_b, nullptr, nullptr, stream));
+        }
+        if (tp)
+            CLI_RT(rt_denoise_variance_device(ctx, out_a, out_b, nullptr, 1, feat0, feat1, feature_samples, width, height, &dv,
+                                              nullptr, rgba8, stream));
+        else
+            CLI_RT(rt_denoise_variance_device(ctx, accum_a, accum_b, half_count, 0, feat0, feat1, feature_samples, width,
+                                              height, &dv, nullptr, rgba8, stream));
+        ++frame_index;
+        return 0;
+    };
+    if (int rc = frame()) return rc;   // warm-up: the adaptive planes and the filters' band buffers exist
+    if (tp) CLI_RT(rt_temporal_reset(temporal, stream));
+    CLI_HIP(hipStreamSynchronize(stream));
+    frame_index = 0;
+    const double pixels = double(width) * height;
+    uint32_t done = 0;
+    while (done < frames) {
+        const auto b = std::chrono::steady_clock::now();
+        uint32_t k = 0;
+        window_feedback = 0;
+        for (;;) {
+            if (int rc = frame()) return rc;
+            ++k;
+            if (done + k >= frames) break;
+            if (std::chrono::steady_clock::now() - b > std::chrono::milliseconds(1000)) break;
+        }
+        CLI_HIP(hipStreamSynchronize(stream));
+        const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - b).count();
+        done += k;
+        if (window_feedback) CLI_RT(rt_sample_map_get_info(map, &map_info));   // (the stream is idle)
+        std::string stage;
+        if (tp) stage = ", temporal history " + std::to_string(tp->max_history) + (reproject ? " reprojected" : "");
+        std::printf("duration_per_frame: %.3f ms (%u frames, adaptive, threshold %g: %u feedback frames, next map mean %.2f spp "
+                    "of at most %u%s, variance-guided denoise: %u feature samples)\n",
+                    sec / k * 1e3, k, double(ad.threshold), window_feedback, double(map_info.samples) / pixels, samples,
+                    stage.c_str(), feature_samples);
+    }
+    if (store) {   // the last frame's filtered image
+        std::vector<uint8_t> img(texels * 4);
+        CLI_HIP(hipMemcpy(img.data(), rgba8, img.size(), hipMemcpyDeviceToHost));
+        CLI_RT(rt_store_ppm("render.ppm", img.data(), width, height));
+    }
+    rt_temporal_destroy(temporal);
+    rt_motion_destroy(motion);
+    rt_sample_map_destroy(map);
+    rt_context_destroy(ctx);
+    (void)hipStreamDestroy(stream);
+    for (float* p : {accum, accum_a, accum_b, feat0, feat1, out_a, out_b, motion_plane}) (void)hipFree(p);
+    (void)hipFree(half_count);
+    (void)hipFree(rgba8);
+    return 0;
+}
+
 // F[,ITER]
 bool parse_denoise(const char* s, uint32_t& f, uint32_t& iter) {
     const std::string v = s;
@@ -625,7 +777,8 @@ int main(int argc, const char** argv) {
             std::puts("                                  # launch of a block table per replayed frame");
             std::puts("--feedback                        # With --adaptive and --frames: every frame after the first renders");
             std::puts("                                  # the previous frame's map, measures its noise and plans the next");
-            std::puts("                                  # map on the GPU (not with --replay)");
+            std::puts("                                  # map on the GPU (not with --replay); with --denoise-variance, and");
+            std::puts("                                  # optionally --temporal, every frame's two halves feed the filters");
             std::puts("--denoise [<F>[,<iter>]]          # One GPU, hash stream, one frame: first-hit features of F samples");
             std::puts("                                  # per pixel (default 16), then iter edge-avoiding filter passes");
             std::puts("                                  # (default 3); --store writes the denoised image");
@@ -750,6 +903,8 @@ int main(int argc, const char** argv) {
             return 2;
         }
     }
+    // the one pairing of noise-driven frames with the filters: the feedback loop hands its halves over
+    const bool feedback_filtered = feedback && adaptive && frames > 0 && denoise_variance && !denoise;
     if (reproject && !temporal) {
         std::fprintf(stderr, "--reproject moves the history of --temporal: it needs --temporal\n");
         return 2;
@@ -771,11 +926,11 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--temporal runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
-        if (adaptive) {
+        if (adaptive && !feedback_filtered) {
             std::fprintf(stderr, "--temporal renders plain frames: it cannot run with --adaptive\n");
             return 2;
         }
-        if (!(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
+        if (!feedback_filtered && !(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
             std::fprintf(stderr, "--temporal needs the counter-based stream: give --rng hash\n");
             return 2;
         }
@@ -794,7 +949,7 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--denoise-variance is a filter of its own: it cannot run with --denoise\n");
             return 2;
         }
-        if (adaptive) {
+        if (adaptive && !feedback_filtered) {
             std::fprintf(stderr, "--denoise-variance renders two plain halves: it cannot run with --adaptive\n");
             return 2;
         }
@@ -802,11 +957,16 @@ int main(int argc, const char** argv) {
             std::fprintf(stderr, "--denoise-variance runs on one GPU: it cannot run with --gpus %u\n", gpu_count);
             return 2;
         }
-        if (frames > 0 && !temporal) {
+        if (frames > 0 && !temporal && !feedback_filtered) {
             std::fprintf(stderr, "--denoise-variance renders one frame: it cannot run with --frames\n");
             return 2;
         }
-        if (!(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
+        if (feedback_filtered && uint64_t(frames) * samples > 0xffffffffull) {
+            std::fprintf(stderr, "--feedback with --denoise-variance gives every frame a sample range of its own: "
+                                 "--frames %u x --samples %u exceeds 32 bits\n", frames, samples);
+            return 2;
+        }
+        if (!feedback_filtered && !(rng_explicit && rng_mode == RT_RNG_SAMPLE_HASH)) {
             std::fprintf(stderr, "--denoise-variance needs the counter-based stream: give --rng hash\n");
             return 2;
         }
@@ -843,6 +1003,9 @@ int main(int argc, const char** argv) {
         std::fprintf(stderr, "%s\n", rt_last_error());
         return 1;
     }
+    if (feedback_filtered)
+        return run_feedback_filtered_frames(samples, width, height, frames, animate, store, ad, dv_feature_samples, dv,
+                                            temporal ? &tp : nullptr, reproject, camera_step);
     if (temporal) {
         const rt_denoise dn = {denoise_iterations, 4.0f, 16.0f, 1.0f};
         return run_temporal_frames(samples, width, height, frames, animate, store,

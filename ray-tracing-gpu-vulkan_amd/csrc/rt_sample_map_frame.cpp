@@ -526,7 +526,8 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
         prev = level;
     }
     if (hipError_t e = rt::launch_adaptive_resolve(a.planes, a.planes + 3u * texels, texels, band_width, P.tiles_x,
-                                                   map->table + map->n_tiles, accum, out, sample_count, st);
+                                                   map->table + map->n_tiles, accum, out, sample_count, nullptr, nullptr,
+                                                   nullptr, st);
         e != hipSuccess)
         return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
     RT_HIP(hipEventRecord(map->ev_read, st));   // the next set call waits for this frame
@@ -534,16 +535,21 @@ int rt_render_sample_map_device(rt_context* ctx, const RenderCallInfo* rci, cons
     return render_issued(ctx, st);
 }
 
+}  // extern "C"
+
+namespace {
+
 // A feedback frame: the map's A half into planes A and its B half into planes B
 // (two table launches sized on the device), the update (the next counts from the two halves'
 // difference), the resolve (A + B by the map's counts; zeroes both) and the planner in halves mode
 // on the next counts. Everything is queued; the context orders it behind whatever it queued before,
 // so the one table of the map is rebuilt only after the frames that read it.
-int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
-                                         uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
-                                         uint32_t* sample_count, const rt_options* opt, rt_sample_map* map,
-                                         const rt_sample_map_feedback* fb, uint64_t* d_tile_error, void* stream) {
-    static const char* const who = "rt_render_sample_map_feedback_device";
+// `halves` (rt_render_sample_map_feedback_halves_device, checked by the caller; null: the plain call):
+// the resolve also writes the two halves and the half counts.
+int feedback_frame(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows, uint32_t band_width,
+                   uint32_t band_height, float* accum, uint8_t* out, uint32_t* sample_count, const rt_options* opt,
+                   rt_sample_map* map, const rt_sample_map_feedback* fb, uint64_t* d_tile_error,
+                   const rt_half_outputs* halves, void* stream, const char* who) {
     rt_options o{};
     bool empty = false;
     if (int rc = check_render_args(ctx, rci, band_width, band_height, accum, out, opt, who, o, &empty)) return rc;
@@ -610,12 +616,36 @@ int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* 
     if (hipError_t e = rt::launch_feedback_update(F, st); e != hipSuccess)
         return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_feedback_update: ") + hipGetErrorString(e)));
     if (hipError_t e = rt::launch_adaptive_resolve(half[0], half[1], texels, band_width, P.tiles_x, map->table + n, accum, out,
-                                                   sample_count, st);
+                                                   sample_count, halves ? halves->accum_a : nullptr,
+                                                   halves ? halves->accum_b : nullptr,
+                                                   halves ? halves->half_count : nullptr, st);
         e != hipSuccess)
         return abort_on_planes(ctx, st, fail(RT_ERR_DEVICE, std::string("launch_adaptive_resolve: ") + hipGetErrorString(e)));
     if (int rc = render_issued(ctx, st)) return rc;
     // the next frame's table, from the counts the update chose (<= max_spp <= cap)
     return queue_device_plan(map, nullptr, fb->unit_samples, cap, true, st, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_sample_map_feedback_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                         uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                                         uint32_t* sample_count, const rt_options* opt, rt_sample_map* map,
+                                         const rt_sample_map_feedback* fb, uint64_t* d_tile_error, void* stream) {
+    return feedback_frame(ctx, rci, rows, band_width, band_height, accum, out, sample_count, opt, map, fb, d_tile_error,
+                          nullptr, stream, "rt_render_sample_map_feedback_device");
+}
+
+int rt_render_sample_map_feedback_halves_device(rt_context* ctx, const RenderCallInfo* rci, const uint32_t* rows,
+                                                uint32_t band_width, uint32_t band_height, float* accum, uint8_t* out,
+                                                uint32_t* sample_count, const rt_options* opt, rt_sample_map* map,
+                                                const rt_sample_map_feedback* fb, uint64_t* d_tile_error,
+                                                const rt_half_outputs* halves, void* stream) {
+    if (int rc = rt::half_outputs_check(halves, accum)) return rc;
+    return feedback_frame(ctx, rci, rows, band_width, band_height, accum, out, sample_count, opt, map, fb, d_tile_error,
+                          halves, stream, "rt_render_sample_map_feedback_halves_device");
 }
 
 int rt_debug_sample_map_feedback(rt_sample_map* map, uint32_t* next, uint64_t* raised, uint64_t* lowered) {

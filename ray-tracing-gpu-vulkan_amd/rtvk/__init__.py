@@ -32,7 +32,7 @@ __all__ = [
     "partition_tile_rows", "multi_plan_adaptive", "SampleMap", "sample_map_plan", "sample_map_info", "sample_map_block_plan",
     "sample_map_device_capacity", "sample_map_device_unit", "sample_map_feedback_count", "hand_out", "make_feedback",
     "make_denoise", "denoise_check", "make_denoise_variance", "denoise_variance_check",
-    "Temporal", "make_temporal", "temporal_check", "Motion", "motion_check",
+    "Temporal", "make_temporal", "temporal_check", "Motion", "motion_check", "half_outputs_check",
 ]
 
 STREAM = abi.RT_RNG_PIXEL_STREAM   # the reference's per-pixel LCG stream (random.glsl)
@@ -102,6 +102,13 @@ def make_denoise(iterations: int = 3, k_normal: float = 4.0, k_depth: float = 16
     d = abi.Denoise()
     d.iterations, d.k_normal, d.k_depth, d.k_color = iterations, k_normal, k_depth, k_color
     return d
+
+
+def half_outputs_check(halves: Optional["abi.HalfOutputs"], accum_ptr: Optional[int] = None) -> None:
+    """rt_half_outputs_check (host only): raises RtError where a halves frame would refuse its
+    rt_half_outputs beside `accum_ptr`, the address of the frame's accumulator (pointers are compared,
+    nothing is read)."""
+    check(load_library().rt_half_outputs_check(ctypes.byref(halves) if halves is not None else None, accum_ptr))
 
 
 def denoise_check(params: Optional["abi.Denoise"], band_w: int, band_h: int, feature_samples: int) -> None:
@@ -345,14 +352,37 @@ class Renderer:
                                          ctypes.byref(options) if options is not None else None,
                                          _stream_ptr(stream, self.device)))
 
+    @staticmethod
+    def _half_outputs(accum_a, accum_b, half_count, bh: int, bw: int) -> Optional["abi.HalfOutputs"]:
+        """The rt_half_outputs of a halves frame, or None when no half output is given. accum_a and
+        accum_b come together; the tensor checks follow accum and sample_count."""
+        if accum_a is None and accum_b is None and half_count is None:
+            return None
+        if accum_a is None or accum_b is None:
+            raise ValueError("give accum_a and accum_b together (half_count needs both)")
+        _check_dev_tensor(accum_a, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(accum_b, "torch.float32", (bh, bw, 4))
+        h = abi.HalfOutputs()
+        h.accum_a, h.accum_b, h.half_count, h.reserved = accum_a.data_ptr(), accum_b.data_ptr(), None, None
+        if half_count is not None:
+            if not half_count.is_cuda or half_count.element_size() != 4 or half_count.is_floating_point() \
+                    or not half_count.is_contiguous() or tuple(half_count.shape) != (bh, bw):
+                raise ValueError("half_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+            h.half_count = half_count.data_ptr()
+        return h
+
     def render_adaptive(self, rci: RenderCallInfo, accum, out, sample_count=None, rows=None,
                         options: Optional[Options] = None, adaptive: Optional[Adaptive] = None,
-                        stream=None) -> AdaptiveInfo:
+                        stream=None, accum_a=None, accum_b=None, half_count=None) -> AdaptiveInfo:
         """One band rendered to a noise level (rt_render_adaptive_device): `adaptive` from
         make_adaptive(), rci.samplesPerRenderCall the cap, options with rng_mode HASH. Tensors as
         render_device; sample_count: optional 4-byte integer cuda tensor [band_h, band_w] that
         receives each texel's sample count. Ordered on `stream`, but blocks the host once per pass;
-        the outputs are valid once `stream` completes. Returns the frame's AdaptiveInfo."""
+        the outputs are valid once `stream` completes. Returns the frame's AdaptiveInfo.
+        accum_a, accum_b (float32 [band_h, band_w, 4], together) and the optional half_count (4-byte
+        integer [band_h, band_w]) make it a halves frame (rt_render_adaptive_halves_device): they
+        receive the frame's two half accumulators and n / 2 per texel, as denoise_variance and the
+        temporal calls read them (sample_count=half_count there)."""
         if adaptive is None:
             raise ValueError("adaptive is required (make_adaptive)")
         bh, bw = int(accum.shape[0]), int(accum.shape[1])
@@ -370,6 +400,14 @@ class Renderer:
                 raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
             count_ptr = sample_count.data_ptr()
         info = AdaptiveInfo()
+        halves = self._half_outputs(accum_a, accum_b, half_count, bh, bw)
+        if halves is not None:
+            check(self._lib.rt_render_adaptive_halves_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
+                                                             accum.data_ptr(), out.data_ptr(), count_ptr,
+                                                             ctypes.byref(options) if options is not None else None,
+                                                             ctypes.byref(adaptive), ctypes.byref(info),
+                                                             ctypes.byref(halves), _stream_ptr(stream, self.device)))
+            return info
         check(self._lib.rt_render_adaptive_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
                                                   accum.data_ptr(), out.data_ptr(), count_ptr,
                                                   ctypes.byref(options) if options is not None else None,
@@ -411,13 +449,16 @@ class Renderer:
                                                     _stream_ptr(stream, self.device)))
 
     def render_sample_map_feedback(self, rci: RenderCallInfo, accum, out, smap: "SampleMap", feedback, sample_count=None,
-                                   rows=None, options: Optional[Options] = None, tile_error=None, stream=None) -> None:
+                                   rows=None, options: Optional[Options] = None, tile_error=None, stream=None,
+                                   accum_a=None, accum_b=None, half_count=None) -> None:
         """A feedback frame (rt_render_sample_map_feedback_device): smap's counts (rounded up to even)
         render as two halves, each tile's next count follows from their difference by `feedback`
         (make_feedback) and the map is re-planned with those counts on the device; nothing is read
         back. Tensors as render_sample_map; tile_error: optional contiguous int64 cuda tensor
         [tiles, 2] receiving (E, S) per tile. rci.samplesPerRenderCall is the cap: even, >=
-        feedback.max_spp and what the map holds."""
+        feedback.max_spp and what the map holds. accum_a, accum_b and half_count as in render_adaptive
+        (rt_render_sample_map_feedback_halves_device): a tile of count n = 2 h at sample_base b gives
+        accum_a = render_device at h samples from b, accum_b the same from b + h, half_count = h."""
         bh, bw = int(accum.shape[0]), int(accum.shape[1])
         _check_dev_tensor(accum, "torch.float32", (bh, bw, 4))
         _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
@@ -439,6 +480,14 @@ class Renderer:
                     or not tile_error.is_contiguous() or tile_error.numel() != 2 * tiles:
                 raise ValueError(f"tile_error must be a contiguous 8-byte integer cuda tensor of 2 x {tiles} entries")
             err_ptr = tile_error.data_ptr()
+        halves = self._half_outputs(accum_a, accum_b, half_count, bh, bw)
+        if halves is not None:
+            check(self._lib.rt_render_sample_map_feedback_halves_device(
+                self._ctx, ctypes.byref(rci), rows_ptr, bw, bh, accum.data_ptr(), out.data_ptr(), count_ptr,
+                ctypes.byref(options) if options is not None else None, smap._map if smap is not None else None,
+                ctypes.byref(feedback) if feedback is not None else None, err_ptr, ctypes.byref(halves),
+                _stream_ptr(stream, self.device)))
+            return
         check(self._lib.rt_render_sample_map_feedback_device(self._ctx, ctypes.byref(rci), rows_ptr, bw, bh,
                                                              accum.data_ptr(), out.data_ptr(), count_ptr,
                                                              ctypes.byref(options) if options is not None else None,
@@ -648,6 +697,23 @@ class Renderer:
         """Diagnostic (rt_debug_denoise_lds_steps): denoise iterations of step <= max_step (0, 1, 2
         or 4, the default) stage their taps in LDS; the image does not depend on it."""
         check(self._lib.rt_debug_denoise_lds_steps(self._ctx, max_step))
+
+    def adaptive_resolve(self, accum, out, count: int, sample_count=None, accum_a=None, accum_b=None, half_count=None,
+                         stream=None) -> None:
+        """Timing (rt_debug_adaptive_resolve): the resolve of adaptive and feedback frames alone, one
+        launch over the context's zero planes with `count` as every tile's count; with accum_a and
+        accum_b the resolve that also hands the halves over. Tensors as render_adaptive."""
+        bh, bw = int(accum.shape[0]), int(accum.shape[1])
+        _check_dev_tensor(accum, "torch.float32", (bh, bw, 4))
+        _check_dev_tensor(out, "torch.uint8", (bh, bw, 4))
+        if sample_count is not None and (not sample_count.is_cuda or sample_count.element_size() != 4 or
+                                         not sample_count.is_contiguous() or tuple(sample_count.shape) != (bh, bw)):
+            raise ValueError("sample_count must be a contiguous 4-byte integer cuda tensor [band_h, band_w]")
+        halves = self._half_outputs(accum_a, accum_b, half_count, bh, bw)
+        check(self._lib.rt_debug_adaptive_resolve(self._ctx, bw, bh, count, accum.data_ptr(), out.data_ptr(),
+                                                  None if sample_count is None else sample_count.data_ptr(),
+                                                  ctypes.byref(halves) if halves is not None else None,
+                                                  _stream_ptr(stream, self.device)))
 
     def host_waits(self) -> int:
         """Host waits inside calls documented as queued without one (rt_debug_host_waits)."""

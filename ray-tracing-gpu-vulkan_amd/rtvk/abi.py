@@ -118,6 +118,12 @@ class SampleMapFeedback(ctypes.Structure):
                 ("unit_samples", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class HalfOutputs(ctypes.Structure):
+    """rt_half_outputs (include/rt_mi355x.h): device pointers of a halves frame's extra outputs."""
+    _fields_ = [("accum_a", ctypes.c_void_p), ("accum_b", ctypes.c_void_p), ("half_count", ctypes.c_void_p),
+                ("reserved", ctypes.c_void_p)]
+
+
 class Denoise(ctypes.Structure):
     """rt_denoise (include/rt_mi355x.h)."""
     _fields_ = [("iterations", ctypes.c_uint32), ("k_normal", ctypes.c_float), ("k_depth", ctypes.c_float),
@@ -182,6 +188,7 @@ assert ctypes.sizeof(RenderCallInfo) == 64 and RenderCallInfo.camera_dir.offset 
 assert ctypes.sizeof(Options) == 32
 assert ctypes.sizeof(Adaptive) == 16 and ctypes.sizeof(AdaptiveInfo) == 24 and AdaptiveInfo.samples.offset == 16
 assert ctypes.sizeof(SampleMapInfo) == 32 and SampleMapInfo.samples.offset == 16
+assert ctypes.sizeof(HalfOutputs) == 32 and HalfOutputs.half_count.offset == 16
 assert ctypes.sizeof(Denoise) == 16
 assert ctypes.sizeof(DenoiseVariance) == 20
 assert ctypes.sizeof(TemporalParams) == 16
@@ -226,6 +233,14 @@ EXPORTS = {
     "rt_debug_sample_map_limit_blocks": (_I, [_P, _U64]),
     "rt_render_sample_map_feedback_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
                                                   ctypes.POINTER(Options), _P, ctypes.POINTER(SampleMapFeedback), _P, _P]),
+    "rt_half_outputs_check": (_I, [ctypes.POINTER(HalfOutputs), _P]),
+    "rt_render_adaptive_halves_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
+                                              ctypes.POINTER(Options), ctypes.POINTER(Adaptive),
+                                              ctypes.POINTER(AdaptiveInfo), ctypes.POINTER(HalfOutputs), _P]),
+    "rt_render_sample_map_feedback_halves_device": (_I, [_P, ctypes.POINTER(RenderCallInfo), _P, _U32, _U32, _P, _P, _P,
+                                                         ctypes.POINTER(Options), _P,
+                                                         ctypes.POINTER(SampleMapFeedback), _P,
+                                                         ctypes.POINTER(HalfOutputs), _P]),
     "rt_debug_host_waits": (_I, [_P, ctypes.POINTER(_U64)]),
     "rt_debug_sample_map_feedback": (_I, [_P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     "rt_debug_hand_out": (_I, [_U32, _U64, _U64, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
@@ -308,6 +323,7 @@ EXPORTS = {
     "rt_debug_multi_feedback": (_I, [_P, _P, _U32]),
     "rt_debug_multi_balance_info": (_I, [_P, _P]),
     "rt_debug_denoise_lds_steps": (_I, [_P, _U32]),
+    "rt_debug_adaptive_resolve": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, ctypes.POINTER(HalfOutputs), _P]),
 }
 
 _lib = None
