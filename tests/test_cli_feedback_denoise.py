@@ -76,7 +76,8 @@ def test_refusals_of_the_pairing(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("stage", [(), ("--temporal", "8", "--reproject", "--camera-step", "0.05")], ids=["filter", "reprojected"])
+@pytest.mark.parametrize("stage", [(), ("--temporal", "8", "--reproject", "--camera-step", "0.05"), ("--temporal", "8")],
+                         ids=["filter", "reprojected", "in-place"])
 def test_store_equals_the_python_chain(tmp_path, oracle, stage):
     import torch
     if not torch.cuda.is_available():
@@ -89,10 +90,12 @@ def test_store_equals_the_python_chain(tmp_path, oracle, stage):
     assert lines and sum(int(re.search(r"\((\d+) frames", ln).group(1)) for ln in lines) == 4
     assert sum(int(re.search(r"(\d+) feedback frames", ln).group(1)) for ln in lines) == 3
     assert "variance-guided denoise: 16 feature samples" in lines[-1]
-    assert ("temporal history 8 reprojected" in lines[-1]) == bool(stage)
+    moved = "--reproject" in stage
+    assert ("temporal history 8" in lines[-1]) == bool(stage) and ("reprojected" in lines[-1]) == moved
+    assert ("temporal history 8 reprojected" in lines[-1]) == moved
     img = read_ppm(tmp_path / "render.ppm", W, H)
-    res = gpu_chain(rtvk, torch, oracle, 4, start=None, temporal=bool(stage), reproject=bool(stage),
-                    s=0.05 if stage else 0.0, thr=0.3, lo=4, step_spp=4, cap=64, feature_samples=16, history=8)
+    res = gpu_chain(rtvk, torch, oracle, 4, start=None, temporal=bool(stage), reproject=moved,
+                    s=0.05 if moved else 0.0, thr=0.3, lo=4, step_spp=4, cap=64, feature_samples=16, history=8)
     np.testing.assert_array_equal(img, res[3]["out"][..., :3])
     # the loop did what it says: several counts in the last frame, and the filter changed the image
     assert len(np.unique(res[3]["half"])) >= 3

@@ -87,3 +87,23 @@ def test_temporal_store_equals_the_python_chain(tmp_path, oracle):
     _, _, out, lens = gpu_chain(rtvk, torch, oracle, (0.0, 0.0, 0.0), True)
     assert np.all(lens[2] == 3)                                   # a static scene: every texel valid
     np.testing.assert_array_equal(img, out[..., :3])
+
+
+@pytest.mark.gpu
+def test_temporal_store_of_the_plain_filter_equals_the_python_chain(tmp_path, oracle):
+    """--denoise F --temporal N: the plain filter behind the stage, one accumulator per frame."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import rtvk
+    from test_gpu_temporal import CHAIN, gpu_chain
+    W, H = CHAIN["W"], CHAIN["H"]
+    r = run("--denoise", str(CHAIN["F"]), "--temporal", str(CHAIN["N"]), "--rng", "hash", "--frames", "3", "--samples",
+            str(CHAIN["spp"]), "--width", str(W), "--height", str(H), "--store", cwd=tmp_path)
+    assert r.returncode == 0, r.stderr
+    assert f"temporal history {CHAIN['N']}, plain denoise: {CHAIN['F']} feature samples" in r.stdout
+    assert "two halves" not in r.stdout and "reprojected" not in r.stdout
+    img = read_ppm(tmp_path / "render.ppm", W, H)
+    _, _, out, lens = gpu_chain(rtvk, torch, oracle, (0.0, 0.0, 0.0), False)
+    assert np.all(lens[2] == 3)
+    np.testing.assert_array_equal(img, out[..., :3])
