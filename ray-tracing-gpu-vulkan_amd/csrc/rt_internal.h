@@ -109,9 +109,14 @@ constexpr unsigned kCqLdsBytes = (128u * 4u + 4u) * (RT_TRACE_BLOCK / 64u) + 8u 
 // does not fit beside the queue in a two-block budget.
 //   24 576 B queue + 3 072 B chain counters + 8 192 B gate table + 1 024 B camera terms = 36 864 B.
 // A/B builds: -DRT_BATCH_GATE_LDS=0 keeps the 44-byte entry and the gate's records in
-// L2, -DRT_BATCH_CAMERA_TERMS=0 the generic ray setup and grid entry in generation batches.
+// L2, -DRT_BATCH_CAMERA_TERMS=0 the generic ray setup and grid entry in generation batches,
+// -DRT_BATCH_LEAN_HIT=0 the zeroed hit record and shading defaults of every lane (rt_trace_batch.h
+// batch_segment).
 #ifndef RT_BATCH_GATE_LDS
 #define RT_BATCH_GATE_LDS 1
+#endif
+#ifndef RT_BATCH_LEAN_HIT
+#define RT_BATCH_LEAN_HIT 1
 #endif
 #ifndef RT_BATCH_CAMERA_TERMS
 #define RT_BATCH_CAMERA_TERMS 1

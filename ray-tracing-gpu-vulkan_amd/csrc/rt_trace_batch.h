@@ -54,6 +54,7 @@ __shared__ float4 s_q_o[RT_TRACE_BLOCK];        // o.xyz, LCG state
 __shared__ float4 s_q_d[RT_TRACE_BLOCK];        // d.xyz (normalised), word
 static_assert(rt::kBatchQueue == 64u, "one queue slot per lane of a wave: slot = wave0 + entry");
 constexpr bool kGateLds = RT_BATCH_GATE_LDS != 0, kCameraTerms = RT_BATCH_CAMERA_TERMS != 0;
+constexpr bool kLeanHit = RT_BATCH_LEAN_HIT != 0;
 #if RT_BATCH_GATE_LDS
 // The winner's gate records by sphere id, {cx, cy, cz, r}: static, so a record's address is 16 bi
 // with no base register (DESIGN.md §4.8 measured what a spilled table base costs). Without the
@@ -129,9 +130,15 @@ __device__ __forceinline__ bool batch_segment(const rt::TraceParams& P, const Ca
     setup_ray<false, CAM>(P, r);
     r.walk = true;
     if (active) walk<false, LAYOUT_GRID, FLAT, CAM>(P, cst, refs, ids, r, n_box, n_sph, n_empty);
-    HitRec hr{};
-    float rad = 0.0f;
+    // LEAN: the record has no value in a lane that loaded none, and the gate's verdict is formed where
+    // the record was loaded, so no lane reads (or zeroes) a record it does not have: twelve moves
+    // per segment less, and fewer registers live across the branch
+    HitRec hr;
+    bool gate_fail = false;
+    [[maybe_unused]] float rad0 = 0.0f;
+    if constexpr (!kLeanHit) hr = HitRec{};
     if (active && r.bi != 0xffffffffu) {
+        float rad;
         if constexpr (kGateLds) {
             // the material records from L2, requested first and not waited for before shading; the
             // gate's record from LDS (shading reads its centre only, so w may hold r)
@@ -145,9 +152,12 @@ __device__ __forceinline__ bool batch_segment(const rt::TraceParams& P, const Ca
             hr = load_hit(geom4, mat4, r.bi);
             rad = P.radius[r.bi];
         }
+        if constexpr (kLeanHit) gate_fail = !aabb_hit(hr.g.x, hr.g.y, hr.g.z, rad, r.o, r.inv);
+        else rad0 = rad;
     }
-    unsigned long long regate =
-        __ballot(active && r.bi != 0xffffffffu && !aabb_hit(hr.g.x, hr.g.y, hr.g.z, rad, r.o, r.inv));
+    if constexpr (!kLeanHit)   // (A/B build: every lane gates the record it has or the zeroed one)
+        gate_fail = active && r.bi != 0xffffffffu && !aabb_hit(hr.g.x, hr.g.y, hr.g.z, rad0, r.o, r.inv);
+    unsigned long long regate = __ballot(gate_fail);
     if (P.force_regate) regate = __ballot(active);
     if (__builtin_expect(regate != 0ull, 0)) {
         regate_brute<false>(P, geom4, lane, regate, r);
@@ -161,9 +171,9 @@ __device__ __forceinline__ bool batch_segment(const rt::TraceParams& P, const Ca
         t.qx = t.qy = t.qz = 0u;
         if constexpr (CAMERA && kGateLds) {
             alt = 0u;
-            more = shade_rec<rt::MODE_HASH, true, true, true>(P, cam, hr, t, r.bi, r.best, r.o, r.d, fresh, &alt);
+            more = shade_rec<rt::MODE_HASH, true, true, true, kLeanHit>(P, cam, hr, t, r.bi, r.best, r.o, r.d, fresh, &alt);
         } else {
-            more = shade_rec<rt::MODE_HASH, true, true>(P, cam, hr, t, r.bi, r.best, r.o, r.d, fresh);
+            more = shade_rec<rt::MODE_HASH, true, true, false, kLeanHit>(P, cam, hr, t, r.bi, r.best, r.o, r.d, fresh);
         }
     }
     return more;

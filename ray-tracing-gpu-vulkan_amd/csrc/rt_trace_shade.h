@@ -152,10 +152,14 @@ __device__ __forceinline__ HitRec load_hit_rec(uint32_t bi) {
 // winner gate's loads (lbvh_loop); unused on a miss.
 // ALT (the camera-batch kernel's generation batches): *alt is set to 1 where the checker texture
 // chose colour 1 (the caller clears it), so the caller knows which material record att came from.
-template <int MODE, bool LSUM, bool FAST = false, bool ALT = false>
+// LEAN (the camera-batch kernel's segments only; every other caller's code is what it was): sd and p
+// have no value on a miss, where nothing reads them (a miss never scatters, and a fresh sample
+// overwrites both), so no lane that hits pays for their defaults.
+template <int MODE, bool LSUM, bool FAST = false, bool ALT = false, bool LEAN = false>
 __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera& cam, const HitRec& hr, Path& ps,
                                           uint32_t bi, float best, V3& o, V3& d, bool& fresh,
                                           uint32_t* alt = nullptr) {
+    static_assert(!LEAN || MODE == rt::MODE_HASH, "camera-batch segments");
     if constexpr (MODE == rt::MODE_PROBE) {   // the closest hit is the answer: no shading, the unit ends
         const size_t i = size_t(ps.px >> 16) * P.band_w + (ps.px & 0xffffu);
         P.probe_out[2 * i] = bi;
@@ -193,14 +197,18 @@ __device__ __forceinline__ bool shade_rec(const rt::TraceParams& P, const Camera
     }
     V3 att;
     bool scatter = false;
-    V3 sd = v3(0.0f, 0.0f, 0.0f);
-    V3 p = o;
+    V3 sd, p;
+    if constexpr (!LEAN) {
+        sd = v3(0.0f, 0.0f, 0.0f);
+        p = o;
+    }
     UTIL(3, true);
     if (bi == 0xffffffffu) {
         att = v3(0.7f, 0.8f, 1.0f);  // shader.rmiss:15
     } else {
         // shader.rint:33/37 hit attribute; shader.rchit:38-49
         UTIL(10, true);
+        if constexpr (LEAN) sd = v3(0.0f, 0.0f, 0.0f);
         p = v3(__builtin_fmaf(best, d.x, o.x), __builtin_fmaf(best, d.y, o.y),
                __builtin_fmaf(best, d.z, o.z));
         const float4 gc4 = hr.g;
