@@ -18,13 +18,21 @@ extern "C" {
 /* Diagnostic (tests only): evaluates one arithmetic-contract primitive on `device` for n
  * (x, y) pairs: op 0 sqrt(x), 1 x/y, 2 sin(x), 3 fma(x,y,1), 4 normalize(x,y,0.5).x, 5 pow(x,5),
  * 6 sample_seed_hash(bits(x), bits(y)) as bits, 7 / 8 low / high word of the 8.24 fixed-point
- * value of colour x, as bits, 9 checker decision at (x, y, 0.5 (x - y)) as 1 / 0. */
+ * value of colour x, as bits, 9 checker decision at (x, y, 0.5 (x - y)) as 1 / 0, 10 normalize(x,y,0.5).y
+ * as the kernels compute it (by sqrt_rcp_cr, length and reciprocal from one v_rsq_f32, in a build with
+ * -DRT_NORMALIZE_RSQ=1), 11 the same by v_sqrt_f32 then v_rcp_f32, which op 10 must equal bit for bit. */
 int rt_debug_math(int device, int op, const float* in_pairs, float* out, uint32_t n);
 /* Diagnostic (tests only): the kernels' cheap correctly rounded operations against hipcc's
  * correctly rounded ones on `device`: rcp_cr(x) vs 1.0f / x and sqrt_cr(x) vs sqrtf(x) over all 2^32
  * binary32 inputs (mismatches3[0], [1]; NaN == NaN), and the camera's float(double(x) * (1 /
  * double(b))) vs x / b for every binary32 x in [0, 65536) and eleven image sizes b (mismatches3[2]). */
 int rt_debug_exact_exhaustive(int device, uint64_t* mismatches3);
+/* Diagnostic (tests only): normalize's length and reciprocal from one v_rsq_f32 (csrc/rt_device_math.h
+ * sqrt_rcp_cr) over all 2^32 binary32 inputs x on `device`, NaN == NaN: out4[0] mismatches of the
+ * length against sqrtf(x), out4[1] of the reciprocal against 1.0f / sqrtf(x), out4[2] of the square
+ * root alone by the same chain (sqrt_rsq) against sqrtf(x), out4[3] the x in [2^-100, 2^100] that
+ * took the rare branch (the v_sqrt_f32 / v_rcp_f32 form). */
+int rt_debug_exact_normalize_exhaustive(int device, uint64_t* out4);
 /* Durations (ms) of the trace kernel of ctx's most recent launches (at most 64 are kept), oldest
  * first, from HIP events recorded on the launch stream around the kernel itself (not the resolve):
  * a caller times K launches inside its own timed region and reads them afterwards. *count =

@@ -1660,6 +1660,23 @@ int rt_debug_exact_exhaustive(int device, uint64_t* mismatches3) {
     return RT_OK;
 }
 
+int rt_debug_exact_normalize_exhaustive(int device, uint64_t* out4) {
+    if (!out4) return fail(RT_ERR_INVALID_ARGUMENT, "NULL buffer");
+    int nd = 0;
+    if (int rc = rt::current_device_count(&nd)) return rc;
+    if (device < 0 || device >= nd) return fail(RT_ERR_INVALID_ARGUMENT, "device index out of range");
+    DeviceGuard g(device);
+    unsigned long long* bad = nullptr;
+    RT_HIP(hipMalloc(&bad, 4 * sizeof(unsigned long long)));
+    RT_HIP(hipMemset(bad, 0, 4 * sizeof(unsigned long long)));
+    RT_HIP(rt::launch_debug_exact_normalize(bad, nullptr));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    RT_HIP(hipMemcpy(h, bad, sizeof(h), hipMemcpyDeviceToHost));
+    (void)hipFree(bad);
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return RT_OK;
+}
+
 int rt_store_ppm(const char* path, const uint8_t* rgba8, uint32_t width, uint32_t height) {
     if (!path || !rgba8) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
     FILE* f = std::fopen(path, "wb");

@@ -1,6 +1,6 @@
 // rt_debug_kernels.hip — diagnostic kernels that evaluate pieces of the trace kernels on their own:
-// the contract primitives (rt_debug_math_kernel), the exhaustive check of rcp_cr / sqrt_cr and the
-// camera division (rt_debug_exact_kernel), and one bounce of given hits by the frames' own shade_rec
+// the contract primitives (rt_debug_math_kernel), the exhaustive checks of rcp_cr / sqrt_cr and the
+// camera division (rt_debug_exact_kernel) and of normalize's sqrt_rcp_cr (rt_debug_exact_normalize_kernel), and one bounce of given hits by the frames' own shade_rec
 // (rt_scatter_probe_kernel: shader.rchit:38-133); with their launchers. It includes the unit and
 // shading headers and none of the walks.
 #include <hip/hip_runtime.h>
@@ -34,6 +34,8 @@ __global__ void rt_debug_math_kernel(int op, const float* __restrict__ in, float
         case 7: r = __uint_as_float(sample_fixed(x)); break;
         case 8: r = 0.0f; break;   // high word of the (32-bit) per-sample value
         case 9: r = checker_positive(x, y, 0.5f * (x - y)) ? 1.0f : 0.0f; break;
+        case 10: { V3 v = normalize(v3(x, y, 0.5f)); r = v.y; break; }
+        case 11: { V3 v = normalize_sqrt_rcp(v3(x, y, 0.5f)); r = v.y; break; }
         default: r = 0.0f;
     }
     out[i] = r;
@@ -103,6 +105,30 @@ __global__ __launch_bounds__(256) void rt_debug_exact_kernel(uint64_t base, floa
     }
 }
 
+// Diagnostic: sqrt_rcp_cr (normalize's length and reciprocal from one v_rsq_f32) and sqrt_rsq against
+// hipcc's correctly rounded sqrtf(x) and 1.0f / sqrtf(x) over all 2^32 inputs (base .. base + grid *
+// 256), NaN equals NaN: mismatches of the length in bad[0], of the reciprocal in bad[1], of sqrt_rsq
+// in bad[2]; bad[3] counts the x in [2^-100, 2^100] that took sqrt_rcp_cr's rare branch.
+__global__ __launch_bounds__(256) void rt_debug_exact_normalize_kernel(uint64_t base, unsigned long long* bad) {
+    const uint32_t bits = uint32_t(base + uint64_t(blockIdx.x) * blockDim.x + threadIdx.x);
+    const float x = __uint_as_float(bits);
+    float len, inv;
+    bool rare;
+    sqrt_rcp_cr(x, len, inv, &rare);
+    const float s2 = sqrt_rsq(x), s1 = __builtin_sqrtf(x), r1 = 1.0f / s1;
+    const bool lb = __float_as_uint(len) != __float_as_uint(s1) && !(len != len && s1 != s1);
+    const bool rb = __float_as_uint(inv) != __float_as_uint(r1) && !(inv != inv && r1 != r1);
+    const bool sb = __float_as_uint(s2) != __float_as_uint(s1) && !(s2 != s2 && s1 != s1);
+    const bool in_range = !(bits - 0x0d800000u > 0x71800000u - 0x0d800000u);
+    const unsigned long long ml = __ballot(lb), mr = __ballot(rb), ms = __ballot(sb), mo = __ballot(rare && in_range);
+    if (lane_id() == 0 && (ml | mr | ms | mo)) {
+        atomicAdd(&bad[0], (unsigned long long)__popcll(ml));
+        atomicAdd(&bad[1], (unsigned long long)__popcll(mr));
+        atomicAdd(&bad[2], (unsigned long long)__popcll(ms));
+        atomicAdd(&bad[3], (unsigned long long)__popcll(mo));
+    }
+}
+
 }  // namespace
 
 // ---- host-callable launchers (rt_launchers.h) -----------------------------------------------
@@ -117,6 +143,13 @@ hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st) {
     for (float b : divs)
         for (uint64_t base = 0; base < 0x47800000ull; base += uint64_t(grid) * 256u)
             hipLaunchKernelGGL(rt_debug_exact_kernel, dim3(grid), dim3(256), 0, st, base, b, bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_debug_exact_normalize(unsigned long long* bad, hipStream_t st) {
+    const uint32_t grid = 1u << 22;   // 2^30 inputs per launch, 4 launches
+    for (uint64_t base = 0; base < (1ull << 32); base += uint64_t(grid) * 256u)
+        hipLaunchKernelGGL(rt_debug_exact_normalize_kernel, dim3(grid), dim3(256), 0, st, base, bad);
     return hipGetLastError();
 }
 

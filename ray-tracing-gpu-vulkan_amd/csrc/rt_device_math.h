@@ -44,7 +44,7 @@ __device__ __forceinline__ float rcp_cr(float x) {
 // two neighbours (the same correction hipcc emits, without the denormal scaling and the 0 / inf
 // class fix-up, which this range never needs). Other inputs take __builtin_sqrtf. Bit-identical
 // to it for all 2^32 inputs (scripts/exact_math_exhaustive.hip).
-__device__ __forceinline__ float sqrt_cr(float x) {
+__device__ __forceinline__ float sqrt_cr_hw(float x) {
     const uint32_t ux = __float_as_uint(x);
     const float s = __builtin_amdgcn_sqrtf(x);
     const float sm = __uint_as_float(__float_as_uint(s) - 1u);
@@ -57,15 +57,102 @@ __device__ __forceinline__ float sqrt_cr(float x) {
     return t;
 }
 
+// RT_SQRT_RSQ: sqrt_cr from v_rsq_f32 (sqrt_rsq) instead of v_sqrt_f32 (sqrt_cr_hw): config 3 -1.3 %.
+// RT_NORMALIZE_RSQ: normalize's length and reciprocal from one v_rsq_f32 (sqrt_rcp_cr): exact, and
+// within the run-to-run spread on config 3, so off.
+#ifndef RT_SQRT_RSQ
+#define RT_SQRT_RSQ 1
+#endif
+#ifndef RT_NORMALIZE_RSQ
+#define RT_NORMALIZE_RSQ 0
+#endif
+
+// The Goldschmidt chain hipcc emits for a correctly rounded f32 sqrt with denormals flushed, from the
+// hardware's reciprocal square root (v_rsq_f32, within 1 ulp): s converges to sqrt(x) and h to
+// 1 / (2 sqrt(x)) together, and the exact fma residual d = x - s s, scaled by h, is the last
+// correction of s. Valid for x in [2^-100, 2^100] (no intermediate leaves the normal range); the
+// callers test the range.
+__device__ __forceinline__ void rsq_chain(float x, float& s, float& h) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    s = x * r;
+    h = 0.5f * r;
+    const float e = __builtin_fmaf(-h, s, 0.5f);
+    h = __builtin_fmaf(h, e, h);
+    s = __builtin_fmaf(s, e, s);
+    const float d = __builtin_fmaf(-s, s, x);
+    s = __builtin_fmaf(d, h, s);
+}
+
+// sqrt_cr's contract from the chain above instead of v_sqrt_f32 and its neighbours' residuals: no
+// select and one VALU less. Bit-identical to __builtin_sqrtf for all 2^32 inputs
+// (rt_debug_exact_normalize_exhaustive, out4[2]).
+__device__ __forceinline__ float sqrt_rsq(float x) {
+    const uint32_t ux = __float_as_uint(x);
+    float s, h;
+    rsq_chain(x, s, h);
+    if (__builtin_expect(ux - 0x0d800000u > 0x71800000u - 0x0d800000u, 0)) s = __builtin_sqrtf(x);   // outside [2^-100, 2^100]
+    return s;
+}
+
+__device__ __forceinline__ float sqrt_cr(float x) {
+#if RT_SQRT_RSQ
+    return sqrt_rsq(x);
+#else
+    return sqrt_cr_hw(x);
+#endif
+}
+
+// len = sqrt_cr(x) and inv = rcp_cr(len), bit for bit, from one transcendental: for x in
+// [2^-100, 2^100] the chain's s is the correctly rounded square root and 2 h a reciprocal of it good
+// enough that two Newton steps with the exact residual e = 1 - s q end on the correctly rounded
+// 1 / s. Two, because one leaves three x per pair of binades wrong on the hardware (mantissas
+// 0x0d8936, 0x1fb52d, 0x1fb52f at an even exponent), and testing for them costs more
+// than the second step's two fmas. The one exception of the iteration itself, a divisor with an
+// all-ones mantissa (Markstein), joins the out-of-range inputs (0, negative, NaN, inf, denormal,
+// huge) in one rarely entered branch, formed as rcp_cr forms its own, which recomputes both by
+// v_sqrt_f32 and v_rcp_f32 as before. `rare`, when given, reports that the branch was taken.
+// Bit-identical to sqrtf(x) and 1.0f / sqrtf(x) for all 2^32 inputs (rt_debug_exact_normalize_exhaustive,
+// tests/test_gpu_exact_normalize.py).
+__device__ __forceinline__ void sqrt_rcp_cr(float x, float& len, float& inv, bool* rare = nullptr) {
+    const uint32_t ux = __float_as_uint(x);
+    float s, h;
+    rsq_chain(x, s, h);
+    float q = h + h;
+    float e = __builtin_fmaf(-s, q, 1.0f);
+    q = __builtin_fmaf(e, q, q);
+    e = __builtin_fmaf(-s, q, 1.0f);
+    q = __builtin_fmaf(e, q, q);
+    const bool out = (ux - 0x0d800000u > 0x71800000u - 0x0d800000u)        // outside [2^-100, 2^100]
+                     | (((__float_as_uint(s) + 1u) & 0x7fffffu) == 0u);    // len = 1.11..1 x 2^k
+    if (__builtin_expect(out, 0)) {
+        s = sqrt_cr_hw(x);
+        q = rcp_cr(s);
+    }
+    if (rare) *rare = out;
+    len = s;
+    inv = q;
+}
+
 // dot(a,b) = fma(a.z,b.z, fma(a.y,b.y, a.x*b.x))
 __device__ __forceinline__ float dot(V3 a, V3 b) {
     return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));
 }
-// normalize(v) = v * (1 / sqrt(dot(v,v)))   (both correctly rounded)
-__device__ __forceinline__ V3 normalize(V3 v) {
-    float len = sqrt_cr(dot(v, v));
+// normalize(v) = v * (1 / sqrt(dot(v,v)))   (both correctly rounded), by v_sqrt_f32 and v_rcp_f32:
+// the form frames run, and sqrt_rcp_cr's bit-for-bit reference (rt_debug_math op 11).
+__device__ __forceinline__ V3 normalize_sqrt_rcp(V3 v) {
+    float len = sqrt_cr_hw(dot(v, v));
     float inv = rcp_cr(len);
     return v3(v.x * inv, v.y * inv, v.z * inv);
+}
+// normalize(v) = v * (1 / sqrt(dot(v,v)))   (both correctly rounded)
+__device__ __forceinline__ V3 normalize(V3 v) {
+#if RT_NORMALIZE_RSQ
+    float len, inv;
+    sqrt_rcp_cr(dot(v, v), len, inv);
+    return v3(v.x * inv, v.y * inv, v.z * inv);
+#else
+    return normalize_sqrt_rcp(v);
+#endif
 }
 // GLSL reflect(I, N) = I - 2.0 * dot(N, I) * N
 __device__ __forceinline__ V3 reflect(V3 i, V3 n) {

@@ -35,6 +35,7 @@ hipError_t launch_gather_rows(const float* src_acc, const uint32_t* rows, uint32
 // rt_debug_kernels.hip
 hipError_t launch_debug_math(int op, const float* in, float* out, uint32_t n, hipStream_t st);
 hipError_t launch_debug_exact(unsigned long long* bad, hipStream_t st);
+hipError_t launch_debug_exact_normalize(unsigned long long* bad4, hipStream_t st);
 hipError_t launch_scatter_probe(const ScatterProbeParams& K, bool rec, hipStream_t st);
 // rt_adaptive.hip
 hipError_t launch_adaptive_init(AdaptiveState* state, hipStream_t st);

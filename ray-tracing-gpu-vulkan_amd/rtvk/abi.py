@@ -294,6 +294,7 @@ EXPORTS = {
     "rt_debug_stamps": (_I, [_P, _P]),
     "rt_debug_util": (_I, [_P, _P]),
     "rt_debug_exact_exhaustive": (_I, [ctypes.c_int, _P]),
+    "rt_debug_exact_normalize_exhaustive": (_I, [ctypes.c_int, _P]),
     "rt_debug_launch_info": (_I, [_P, _P]),
     "rt_debug_launch_plan": (_I, [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64]),
     "rt_debug_camera_batches": (_I, [_P, ctypes.c_uint64, ctypes.c_double, _U32, _U32, _I, ctypes.POINTER(_U32)]),
