@@ -83,8 +83,9 @@ void size_lds_forms(const Inputs& in, Plan& p) {
 
 // Kernel form of a launch (rt_internal.h ACCEL_*) and its dynamic LDS bytes. form =
 // options.reserved[1] (A/B and tests, 0 = automatic): 6 one LDS node copy, 8 octant copies, 10
-// every node from L2, 12 the grid, 14 the grid with the wave-cooperative walk; cam_r = the camera's
-// distance from the origin (the grid's margin covers cameras within its pad radius).
+// every node from L2, 12 the grid, 14 the grid with the wave-cooperative walk, 16 the grid in LDS
+// with the wave-wide candidate queue; cam_r = the camera's distance from the origin (the grid's
+// margin covers cameras within its pad radius).
 uint32_t choose_accel(const Inputs& in, const Plan& p, bool brute, uint32_t form, float cam_r, size_t* lds_out) {
     const Tuning& tu = in.tune;
     uint32_t accel;

@@ -1,7 +1,10 @@
 """CPU model of an adaptive frame (rt_render_adaptive_device), built on the
 unchanged oracle: the per-sample integer cube Q[s, y, x, c] of the counter-based stream, the pass
 loop simulated on it with Python ints, and the expected frame stitched from oracle.render(spp=n).
-Helper module of test_adaptive.py and test_cli_adaptive.py (no tests here)."""
+Helper module of test_adaptive.py and test_cli_adaptive.py (no tests here).
+
+A scene is named by `k`: generate_scene's grid half extent, or the name of a scene handed to
+register(); the cubes and frames are cached once per scene either way."""
 import functools
 
 import numpy as np
@@ -9,9 +12,23 @@ import numpy as np
 HASH = 2
 
 
+_REGISTERED = {}
+
+
+def register(name, spheres):
+    """Makes `spheres` the scene of the key `name` (a string) for scene(), cube() and expected_frame().
+    A name keeps the spheres it was first given."""
+    held = _REGISTERED.get(name)
+    if held is None:
+        held = _REGISTERED[name] = np.array(spheres, copy=True)
+        held.setflags(write=False)
+    assert held.shape == np.shape(spheres) and np.array_equal(held, spheres), f"scene {name!r} registered with other spheres"
+    return name
+
+
 @functools.lru_cache(maxsize=None)
 def _scene(oracle, k):
-    return oracle.generate_scene(0.0, k)
+    return _REGISTERED[k] if isinstance(k, str) else oracle.generate_scene(0.0, k)
 
 
 def scene(oracle, k=11):

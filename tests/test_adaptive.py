@@ -127,7 +127,11 @@ def renderer(lib, torch):
 
 
 def gpu_adaptive(lib, renderer, torch, oracle, W, H, k=11, accel=AUTO, rows=None, base=0, image=None, thr=THR,
-                 mn=MIN, step=STEP, mx=MAX, set_scene=True):
+                 mn=MIN, step=STEP, mx=MAX, set_scene=True, options=None):
+    """`k`: the scene's key in adaptive_sim; `options`: ready-made rt_options (their accel and reserved
+    words; the stream and the sample base are set here)."""
+    opt = lib.make_options(accel=accel) if options is None else type(options).from_buffer_copy(options)
+    opt.rng_mode, opt.sample_base = HASH, base
     if set_scene:
         renderer.set_scene(sim.scene(oracle, k))
     iw, ih = image if image else (W, H)
@@ -137,8 +141,7 @@ def gpu_adaptive(lib, renderer, torch, oracle, W, H, k=11, accel=AUTO, rows=None
     cnt = torch.full((H, W), -1, dtype=torch.int32, device="cuda")
     rows_t = None if rows is None else torch.from_numpy(np.asarray(rows, np.int32)).cuda()
     info = renderer.render_adaptive(rci, acc, out, sample_count=cnt, rows=rows_t,
-                                    options=lib.make_options(rng_mode=HASH, accel=accel, sample_base=base),
-                                    adaptive=lib.make_adaptive(thr, mn, step))
+                                    options=opt, adaptive=lib.make_adaptive(thr, mn, step))
     torch.cuda.synchronize()
     return acc.cpu().numpy(), out.cpu().numpy(), cnt.cpu().numpy().astype(np.uint32), info
 
@@ -164,7 +167,7 @@ def assert_frame(got, counts, info_sim, ref):
 
 def parity(lib, renderer, torch, oracle, W, H, vacuous_check=True, **kw):
     """One adaptive frame against the simulation and the oracle."""
-    sk = {k: kw[k] for k in ("k", "rows", "base", "image") if k in kw}
+    sk = {k: kw[k] for k in ("k", "rows", "base", "image") if k in kw}   # (`options` in kw goes to gpu_adaptive)
     mn, step, mx = kw.get("mn", MIN), kw.get("step", STEP), kw.get("mx", MAX)
     Q = sim.cube(oracle, W, H, mx, **sk)
     counts, info_sim = sim.simulate(Q, mn, step, mx, lib.threshold_q16(kw.get("thr", THR)))

@@ -15,6 +15,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import form_matrix
+
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).resolve().parent / "golden"
 BRUTE, LBVH = 1, 2
@@ -383,15 +385,8 @@ def test_grid_one_layer_and_layered_forms(rtvk, renderer, torch, oracle, builder
     form) bit for bit; a stack of small spheres from y = 0.2 to 4.6: the general form runs and
     equals the oracle. Both streams, host grid (LDS) and device grid (L2)."""
     W, H = 48, 32
-    base = oracle.generate_scene()[4:5]
-    stack = [oracle.generate_scene()[:1].copy()]   # the ground sphere
-    rng = np.random.default_rng(11)
-    for k in range(240):
-        r = base.copy()
-        r[0, :16].view(np.float32)[:] = [rng.uniform(-4, 4), 0.2 + 4.4 * k / 239, rng.uniform(-4, 4), 0.2]
-        stack.append(r)
     cases = [(oracle.generate_scene(), True, ((13.0, 2.0, 3.0), (0.0, 0.0, 0.0))),
-             (np.concatenate(stack), False, ((9.0, 3.0, -9.0), (0.0, 2.0, 0.0)))]
+             (form_matrix.stack_scene(oracle), False, form_matrix.STACK_CAMERA)]
     for sc, flat, (cam, look) in cases:
         rci = oracle.render_call_info(3, W, H)
         f = rci.view(np.float32)
@@ -621,6 +616,43 @@ def test_multi_logical_devices(rtvk, torch, logical_refs, n, rng_mode):
         m.render(rci, acc, out, options=rtvk.make_options(rng_mode=rng_mode, accumulate=True, sample_base=base))
         torch.cuda.synchronize()
         assert_same(acc.cpu().numpy(), out.cpu().numpy(), ra1, ro1)
+
+
+@pytest.mark.parametrize("rng_mode", [STREAM, HASH])
+def test_multi_logical_device_built(rtvk, torch, oracle, rng_mode):
+    """BASELINE config 5's multi-device layout in small: three logical devices, each building its own
+    tree and grid on the device (RT_BVH_BUILD=gpu) from the 6 404-sphere scene and walking the grid
+    from L2 (grid-global, the scene's default form) through the rows map of its strips. A plain
+    40x96 frame at 2 spp and an accumulating one on top equal the oracle bit for bit."""
+    W, H, n = 40, 96, 3
+    sc = form_matrix.scene(oracle, "k40")
+    rci_np = oracle.render_call_info(2, W, H)
+    rci = rtvk.RenderCallInfo.from_buffer_copy(rci_np.tobytes())
+    base = 2 if rng_mode != STREAM else 0
+    ra0, ro0, rs0 = oracle.render(sc, rci_np, W, H, opts=oracle.options(rng_mode=rng_mode), threads=16)
+    ra1, ro1, _ = oracle.render(sc, rci_np, W, H, accum=ra0, threads=16,
+                                opts=oracle.options(rng_mode=rng_mode, accumulate=1, sample_base=base))
+    with tree_builder("gpu"):
+        with rtvk.Renderer(0) as one:   # what a device of the frame below runs by default
+            one.set_scene(sc)
+            assert one.scene_array(8)["device_built"] and one.launch_info()["form"] == "grid-global"
+        with rtvk.MultiRenderer(n, logical=True) as m:
+            assert m.device_count == n
+            m.tune(balance=0)
+            m.set_scene(sc)
+            acc = torch.full((H, W, 4), -1.0, dtype=torch.float32, device="cuda:0")
+            out = torch.full((H, W, 4), 7, dtype=torch.uint8, device="cuda:0")
+            m.render(rci, acc, out, options=rtvk.make_options(rng_mode=rng_mode))
+            torch.cuda.synchronize()
+            assert_same(acc.cpu().numpy(), out.cpu().numpy(), ra0, ro0)
+            for a, b in zip(m.partition(H), rtvk.partition_strips(n, H)):   # the row-exact strips the frame rendered
+                np.testing.assert_array_equal(a, b)
+            st = m.stats()
+            assert (st.segments, st.samples) == rs0[:2]
+            assert m.info()["launches"] == n
+            m.render(rci, acc, out, options=rtvk.make_options(rng_mode=rng_mode, accumulate=True, sample_base=base))
+            torch.cuda.synchronize()
+            assert_same(acc.cpu().numpy(), out.cpu().numpy(), ra1, ro1)
 
 
 @pytest.mark.parametrize("n", [2, 3])

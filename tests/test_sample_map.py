@@ -76,13 +76,25 @@ def set_map(torch, smap, table, quantum=0):
     return smap.set(torch.from_numpy(np.asarray(table, np.int32)).cuda(), quantum)
 
 
-def queue_map_frame(lib, renderer, torch, oracle, smap, W, H, accel=AUTO, rows=None, base=0, image=None, cap=MAX):
+def frame_options(lib, accel=AUTO, base=0, options=None):
+    """rt_options of a map, feedback or adaptive frame: the hash stream from sample `base`, with `accel`;
+    or, given ready-made `options`, a copy of them (their accel and reserved words) with that stream
+    and base."""
+    if options is None:
+        return lib.make_options(rng_mode=HASH, accel=accel, sample_base=base)
+    o = type(options).from_buffer_copy(options)
+    o.rng_mode, o.sample_base = HASH, base
+    return o
+
+
+def queue_map_frame(lib, renderer, torch, oracle, smap, W, H, accel=AUTO, rows=None, base=0, image=None, cap=MAX,
+                    options=None):
     """Queues one frame of `smap` into fresh sentinel buffers; no synchronisation."""
     iw, ih = image if image else (W, H)
     bufs = sentinels(torch, W, H)
     rows_t = None if rows is None else torch.from_numpy(np.asarray(rows, np.int32)).cuda()
     renderer.render_sample_map(rci_of(lib, oracle, cap, iw, ih), bufs[0], bufs[1], smap, sample_count=bufs[2],
-                               rows=rows_t, options=lib.make_options(rng_mode=HASH, accel=accel, sample_base=base))
+                               rows=rows_t, options=frame_options(lib, accel, base, options))
     return bufs
 
 
@@ -95,7 +107,8 @@ def assert_exact(got, counts, ref):
 
 
 def map_parity(lib, renderer, torch, oracle, W, H, table, quantum=0, k=11, set_scene=True, **kw):
-    """One map frame of `table` against the oracle at the (quantised) counts. Returns the set call's info."""
+    """One map frame of `table` against the oracle at the (quantised) counts. Returns the set call's info.
+    `k`: the scene's key in adaptive_sim; `options` (in kw): ready-made rt_options, see frame_options."""
     if set_scene:
         renderer.set_scene(sim.scene(oracle, k))
     q = max(1, quantum)
@@ -112,16 +125,17 @@ def map_parity(lib, renderer, torch, oracle, W, H, table, quantum=0, k=11, set_s
     return info
 
 
-def adaptive_parity(lib, renderer, torch, oracle, W, H):
-    """An adaptive frame of the existing kind against the simulation and the oracle."""
-    counts, info_sim = sim.simulate(sim.cube(oracle, W, H, MAX), MIN, STEP, MAX, lib.threshold_q16(THR))
+def adaptive_parity(lib, renderer, torch, oracle, W, H, k=11, thr=THR, options=None):
+    """An adaptive frame of the existing kind against the simulation and the oracle (`k`: the scene's
+    key in adaptive_sim, the renderer's current scene; `options`: see frame_options)."""
+    counts, info_sim = sim.simulate(sim.cube(oracle, W, H, MAX, k=k), MIN, STEP, MAX, lib.threshold_q16(thr))
     sim.assert_not_vacuous(counts, MAX)
     bufs = sentinels(torch, W, H)
     info = renderer.render_adaptive(rci_of(lib, oracle, MAX, W, H), bufs[0], bufs[1], sample_count=bufs[2],
-                                    options=lib.make_options(rng_mode=HASH), adaptive=lib.make_adaptive(THR, MIN, STEP))
+                                    options=frame_options(lib, options=options), adaptive=lib.make_adaptive(thr, MIN, STEP))
     torch.cuda.synchronize()
     got = to_host(bufs)
-    assert_exact(got, counts, sim.expected_frame(oracle, counts))
+    assert_exact(got, counts, sim.expected_frame(oracle, counts, k=k))
     assert (info.passes, info.samples, info.tiles_capped) == (info_sim["passes"], info_sim["samples"],
                                                               info_sim["tiles_capped"])
     return counts, got, info

@@ -18,8 +18,8 @@ import pytest
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import adaptive_sim as sim   # noqa: E402
-from test_sample_map import (AUTO, BRUTE, HASH, MAX, ROWS, assert_exact, lib, queue_map_frame, renderer, rci_of,   # noqa: E402
-                             sentinels, set_map, texel_counts, to_host, torch)
+from test_sample_map import (AUTO, BRUTE, HASH, MAX, ROWS, assert_exact, frame_options, lib, queue_map_frame, renderer,   # noqa: E402
+                             rci_of, sentinels, set_map, texel_counts, to_host, torch)
 
 __all__ = ["lib", "renderer", "torch"]
 W, H = 44, 27
@@ -52,13 +52,13 @@ def step(Q, table, thr, lo=LO, hi=HI):
     return nxt, es
 
 
-def queue_feedback(lib, renderer, torch, oracle, smap, w, h, fb, cap=MAX, accel=AUTO, rows=None, base=0, image=None, err=None):
+def queue_feedback(lib, renderer, torch, oracle, smap, w, h, fb, cap=MAX, accel=AUTO, rows=None, base=0, image=None, err=None,
+                   options=None):
     iw, ih = image if image else (w, h)
     bufs = sentinels(torch, w, h)
     rows_t = None if rows is None else torch.from_numpy(np.asarray(rows, np.int32)).cuda()
     renderer.render_sample_map_feedback(rci_of(lib, oracle, cap, iw, ih), bufs[0], bufs[1], smap, fb, sample_count=bufs[2],
-                                        rows=rows_t, options=lib.make_options(rng_mode=HASH, accel=accel, sample_base=base),
-                                        tile_error=err)
+                                        rows=rows_t, options=frame_options(lib, accel, base, options), tile_error=err)
     return bufs
 
 
@@ -80,10 +80,12 @@ def check_halves_table(lib, smap, table, cap, unit=0):
 
 
 def chain(lib, renderer, torch, oracle, frames, thr=THR, lo=LO, hi=HI, start=START, w=W, h=H, k=11, cap=MAX, unit=0,
-          async_start=False, with_error=True, **kw):
+          async_start=False, with_error=True, set_scene=True, **kw):
     """`frames` feedback frames from `start`, each against the simulation. Returns the tables: [start,
-    after frame 1, ...]."""
-    renderer.set_scene(sim.scene(oracle, k))
+    after frame 1, ...]. `k`: the scene's key in adaptive_sim (set_scene=False: it is the renderer's
+    scene already); `options` (in kw): ready-made rt_options, see test_sample_map.frame_options."""
+    if set_scene:
+        renderer.set_scene(sim.scene(oracle, k))
     sk = {key: kw[key] for key in ("rows", "base", "image") if key in kw}
     Q = sim.cube(oracle, w, h, hi, k=k, **sk)
     fb = lib.make_feedback(thr, lo, hi, unit)

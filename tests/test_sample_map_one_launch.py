@@ -27,7 +27,8 @@ TABLE_71 = [1 + (29 * t) % 71 for t in range(72)]   # 9 x 8 tiles, 71 distinct c
 
 def one_launch_parity(lib, renderer, torch, oracle, W, H, table, unit=0, quantum=0, k=11, set_scene=True, **kw):
     """One frame of `table` under ONE_LAUNCH with units of `unit` samples against the oracle. Returns
-    (the set call's info, the map's schedule_info)."""
+    (the set call's info, the map's schedule_info). `k`: the scene's key in adaptive_sim; `options` (in
+    kw): ready-made rt_options, see test_sample_map.frame_options."""
     if set_scene:
         renderer.set_scene(sim.scene(oracle, k))
     q = max(1, quantum)
